@@ -12,13 +12,25 @@ match fill); then (N>1) the gather of the match records to rank 0 over RCCL.  At
 N x 8 GiB, partitioned contiguously across the ranks (weak scaling, BASELINE config 3 at N=8); each rank warms
 up on max_pattern_len-1 bytes left of its seam.
 
-At N=1 the JSON line additionally carries, measured on the same resident haystack after the timed region:
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the outputs of the last
+timed step if --dump-outputs is given, and the JSON line.  With --full, at N=1, the line additionally carries, measured
+on the same resident haystack after the timed region:
+  "cpu_baseline": the oracle's restatement of the reference DFA loop on one host core (and on all of them),
+  "roofline.empirical_peak": a load-only kernel over the very buffer (the same-box streaming ceiling),
+  "costs":   construction / upload time and table memory of configs 2, 4 and 5,
   "engines": the three count engines of the headline workload side by side (kernel ms, GB/s, fraction of HBM peak),
   "also":    the reference's own corpora (English prose / 5 000 dictionary words) and
              BASELINE configs 4 (100k patterns, contiguous NFA; default engine and the literal failure-link walk)
              and 5 (casei LeftmostFirst find_iter), each with its own roofline / kernel_ms.
+(--no-cpu-baseline and --no-also take their parts out of a --full run again.)
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--gib G] [--engine auto|walk|hot] [--chunk B]
+                    [--dump-outputs DIR] [--full]
+
+--dump-outputs DIR writes the ordered match records of the last timed step -- what a caller of the timed path receives --
+as DIR/pattern.npy, DIR/start.npy, DIR/end.npy (float64, one element per record, in the order of the records) and
+DIR/n_matches.npy.  Patterns, haystack and planted occurrences are seeded, so two builds run with the same arguments
+can be compared output for output.
 
 N>1 is launched by the driver through torch.distributed.run (one rank per GPU).  Rank 0 prints ONE JSON
 line.  `roofline` is the dominant kernel (count/scan walk) measured with HIP events on the launch
@@ -57,6 +69,24 @@ def committed_traffic(tag, kernel, gib):
     return None, None, None
 
 
+DUMP_MAX_RECORDS = 2_500_000   # 3 float64 arrays of that many elements: 60 MB
+
+
+def dump_outputs(path, res, match_dtype):
+    """The ordered match records of the last timed step (a uint8 tensor of 24-byte records, or the gathered record array
+    of an N>1 run) as path/pattern.npy, start.npy, end.npy: float64 (exact below 2^53), in record order.  More than
+    DUMP_MAX_RECORDS records are thinned to a fixed, seeded sample of record indices (kept in order); n_matches.npy always
+    holds the full count."""
+    rec = res if isinstance(res, np.ndarray) else res.cpu().numpy().view(match_dtype)
+    n = len(rec)
+    if n > DUMP_MAX_RECORDS:
+        rec = rec[np.sort(np.random.default_rng(0xAC0D).choice(n, DUMP_MAX_RECORDS, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for f in ("pattern", "start", "end"):
+        np.save(os.path.join(path, f + ".npy"), rec[f].astype(np.float64))
+    np.save(os.path.join(path, "n_matches.npy"), np.array([n], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -70,14 +100,22 @@ def main():
                     help="c2 = headline (BASELINE configs[1]); c4 = 100k patterns, contiguous-NFA failure-link walk; "
                          "c5 = 1k patterns, ascii_case_insensitive + LeftmostFirst find_iter (parity-test configs, "
                          "timed here for the record only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the engines / configs 4+5 side measurements (N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: CPU baseline, streaming "
+                         "ceiling, build / upload costs, the other engines, configs 4+5, the reference's corpora (N=1); "
+                         "N>1: lets ACGPU_BENCH_VERIFY=1 compare the gathered records with the CPU oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the match records of the last timed step as DIR/{pattern,start,end,n_matches}.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the engines / configs 4+5 side measurements (N=1)")
     ap.add_argument("--also-steps", type=int, default=10)
     ap.add_argument("--cpu-sample-mib", type=int, default=1024)
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc pass; default: the committed "
                          "profiles/*_pf_pmc.json of the same kernel/config (PMC passes cannot run inside a timed bench)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the timed steps and their line, nothing beside them
+        args.no_cpu_baseline = args.no_also = True
 
     import torch
     import torch.distributed as dist
@@ -251,8 +289,11 @@ def main():
             dist.destroy_process_group()
         return
 
+    if args.dump_outputs:   # before anything below reuses the record buffer
+        dump_outputs(args.dump_outputs, res, ac.MATCH_DTYPE)
+
     verify = None
-    if world > 1 and os.environ.get("ACGPU_BENCH_VERIFY") == "1":
+    if world > 1 and args.full and os.environ.get("ACGPU_BENCH_VERIFY") == "1":
         # parity of the sharded run against the CPU ORACLE (test infrastructure, after the timed region): the whole global
         # haystack regenerated on the host by the oracle's own generator, the same occurrences planted, searched by the
         # oracle's chunk-parallel restatement of the reference loop; the gathered records must equal its stream
@@ -269,11 +310,12 @@ def main():
     if traffic is None and int(prof.engine_used) == 4 and args.patterns == 1000 and args.workload == "c2":
         traffic, traffic_src, _ = committed_traffic("pf", "k_pf_count<false, false>", args.gib)
     # the same-box streaming ceiling: a plain read-only kernel over this very buffer
+    empirical = None   # (a run of its own: --full)
     try:
-        empirical = float(ac.stream_read_gbps(buf[: buf.numel() // 16 * 16], iters=5))
+        if args.full:
+            empirical = float(ac.stream_read_gbps(buf[: buf.numel() // 16 * 16], iters=5))
     except Exception as exc:
         print(f"bench: streaming ceiling unavailable ({exc})", file=sys.stderr)
-        empirical = None
     ms_per_step = dt / args.steps * 1e3
     value = total * args.steps / dt / 1e9
     kernel_ms = float(np.mean(scan_ms))

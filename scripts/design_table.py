@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""DESIGN.md section 4's table rows from a bench.py line (profiles/rNN_bench.json): usage design_table.py <bench.json>"""
+"""DESIGN.md section 4's table rows from a `bench.py --full` line (profiles/rNN_bench.json): usage design_table.py <bench.json>"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 

@@ -10,7 +10,7 @@ GIB=${PMC_GIB:-8}
 run_pass() {  # name, counters...
   local name=$1; shift
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OLDPWD/$OUT/$name" -o pmc -- \
-      python "$OLDPWD/bench.py" --engine "$ENGINE" --gib "$GIB" --steps 1 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} \
+      python "$OLDPWD/bench.py" --engine "$ENGINE" --gib "$GIB" --steps 1 --warmup 1 --full --no-cpu-baseline ${BENCH_ARGS:-} \
       > "$OLDPWD/$OUT/$name.json" 2> "$OLDPWD/$OUT/$name.err")
   echo "$name exit $?"
   python - "$OUT/$name" <<'PY'

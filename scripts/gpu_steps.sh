@@ -27,11 +27,11 @@ for step in "$@"; do
       timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
       log "smoke exit $?"; tail -3 "$OUT/smoke.log" | tee -a "$OUT/summary.txt" ;;
     bench)
-      timeout 600 python bench.py $arg > "$OUT/bench.json" 2> "$OUT/bench.err"
+      timeout 600 python bench.py --full $arg > "$OUT/bench.json" 2> "$OUT/bench.err"
       log "bench exit $?"; tail -c 400 "$OUT/bench.json" | tee -a "$OUT/summary.txt"; echo ;;
     bench_prof)
       (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/prof" -o b -- \
-          python "$ROOT/bench.py" $arg > "$ROOT/$OUT/bench_under_rocprof.json" 2> "$ROOT/$OUT/prof.err")
+          python "$ROOT/bench.py" --full $arg > "$ROOT/$OUT/bench_under_rocprof.json" 2> "$ROOT/$OUT/prof.err")
       log "rocprof exit $?"
       find "$OUT/prof" -name "*kernel_stats.csv" -exec cp {} "$OUT/bench_kernel_stats.csv" \;
       rm -rf "$OUT/prof"; head -8 "$OUT/bench_kernel_stats.csv" | cut -c1-200 ;;
@@ -66,9 +66,9 @@ for step in "$@"; do
       python scripts/step_timeline.py "$OUT/tr_nat" "k_pfx_count<" > "$OUT/nat_step_timeline.txt" 2>&1; rm -rf "$OUT/tr_nat"
       # (the bench lines below cite these files: the same code, the same box)
       for f in pf dfa_tri c4_pfx c4_cnfa_tri c5_pf nat_sherlock nat_enhuge sorted_txt_walk hot lw_ev_teddy3_1pat_common lw_ev_teddy1_16pat_uncommon lw_ev_teddy1_1pat_common lw_ev_teddy1_1pat_uncommon; do cp "$OUT/${f}_pmc.json" "profiles/${ROUND:-r06}_${f}_pmc.json"; done
-      timeout 700 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; log "bench exit $?"; tail -c 300 "$OUT/bench.json"; echo
-      for flags in "" "--no-also --no-cpu-baseline"; do
-        tag=bench; [ -n "$flags" ] && tag=bench_noalso
+      timeout 700 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; log "bench exit $?"; tail -c 300 "$OUT/bench.json"; echo
+      for flags in "--full" ""; do   # the whole line, and the plain run (timed steps only)
+        tag=bench; [ -z "$flags" ] && tag=bench_noalso
         (cd /tmp && timeout 700 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/prof_$tag" -o b -- \
             python "$ROOT/bench.py" $flags > "$ROOT/$OUT/${tag}_under_rocprof.json" 2> "$ROOT/$OUT/prof_$tag.err")
         log "rocprof $tag exit $?"

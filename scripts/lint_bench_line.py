@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Lint of a bench line kept under profiles/ (run it when the profiles are regenerated; it checks ARTIFACTS, not code, so
-it is not part of the test suites): the line printed by `python bench.py` on an MI355X honours the contract bench.py is
+it is not part of the test suites): the line printed by `python bench.py --full` on an MI355X honours the contract bench.py is
 held to -- one JSON object with the metric / value / config of BASELINE.json, a `roofline` whose fraction is achieved /
 peak on algorithmic bytes, a `cpu_baseline` measured on the same box, and `also` / `engines` entries whose arithmetic is
 consistent.  usage: lint_bench_line.py profiles/rNN_bench.json [per-launch csv of k_pf_count + the traced run's line]"""

@@ -18,7 +18,7 @@ def test_sharded_bench_equals_unsharded(world):
     env = dict(os.environ, ACGPU_BENCH_BACKEND="gloo", ACGPU_BENCH_ONE_DEVICE="1", ACGPU_BENCH_VERIFY="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(29610 + world), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--gib", "0.25"]
+           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--gib", "0.25", "--full"]   # --full: the oracle comparison
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
