@@ -119,6 +119,13 @@ unsigned long long* guard_counter() {
 }
 #endif
 
+ScanGeom with_chunk(ScanGeom g, uint32_t chunk) {
+    g.chunk = chunk;
+    g.grid0 = ov_grid_origin(g.emit_lo, chunk);
+    g.n_chunks = ov_grid_chunks(g.emit_lo, g.emit_hi, chunk);
+    return g;
+}
+
 ScanGeom make_geom(const acgpu_automaton* aut, const acgpu_input* in, size_t shard_begin, size_t shard_end,
                    const uint8_t* dhay, size_t halo) {
     ScanGeom g{};
@@ -130,10 +137,8 @@ ScanGeom make_geom(const acgpu_automaton* aut, const acgpu_input* in, size_t sha
     g.cold_floor = in->span_start + mis;
     g.emit_lo = shard_begin + mis;
     g.emit_hi = shard_end + mis;
-    g.chunk = default_chunk(aut, shard_end - shard_begin);
     g.halo = uint32_t(halo);
-    g.grid0 = (g.emit_lo / g.chunk) * g.chunk;
-    g.n_chunks = std::max<uint64_t>(1, (g.emit_hi - g.grid0 + g.chunk - 1) / g.chunk);
+    g = with_chunk(g, default_chunk(aut, shard_end - shard_begin));
     g.emit_start_matches = shard_begin == in->span_start ? 1u : 0u;
 #ifdef ACGPU_GUARD
     g.guard = guard_counter();

@@ -92,7 +92,7 @@ acgpu_status nonoverlapping_guessed(acgpu_automaton* occ, DeviceState* ds, Scrat
         plan_engines(engine_facts(occ, ds)).first != ENG_PF)
         return ACGPU_OK;
     hipStream_t stream = static_cast<hipStream_t>(in->stream);
-    // (the stream's enqueue context is borrowed, as in overlapping_impl; a second host thread on the same stream keeps the regular path)
+    // (the stream's enqueue context is borrowed; a second host thread on the same stream keeps the regular path)
     DeviceState::AsyncCtx* actx = ds->async_ctx(stream);
     std::unique_lock<std::mutex> borrowed(actx->busy, std::try_to_lock);
     if (!borrowed.owns_lock()) return ACGPU_OK;
@@ -130,8 +130,7 @@ acgpu_status nonoverlapping_guessed(acgpu_automaton* occ, DeviceState* ds, Scrat
         // fused order chain: its bucket words are re-zeroed behind the selection; the host waits for the selection only
         if (!actx->fin) HIP_TRY(hipEventCreateWithFlags(&actx->fin, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(actx->fin, stream));
-        HIP_TRY(launch_event_order_zero(guess.rearm_p, guess.rearm_bytes, stream));
-        actx->sc.eo_zero_p = guess.rearm_p; actx->sc.eo_zero_bytes = guess.rearm_bytes;
+        HIP_TRY(actx->sc.order.rezero_behind(guess.rearm_bytes, stream));
         HIP_TRY(hipEventSynchronize(actx->fin));
     } else HIP_TRY(hipStreamSynchronize(stream));
     const uint64_t records = sc->pinned[0], events = sc->pinned[1], selected = sc->pinned[2];
@@ -147,9 +146,7 @@ acgpu_status nonoverlapping_guessed(acgpu_automaton* occ, DeviceState* ds, Scrat
     if (prof) {
         std::memset(prof, 0, sizeof *prof);
         prof->engine_used = ENG_PF; prof->n_matches = selected;
-        float ms = 0;
-        if (actx->ev[128] && actx->ev[129] && hipEventElapsedTime(&ms, actx->ev[128], actx->ev[129]) == hipSuccess) { prof->ms_scan = ms; prof->ms_total = ms; }
-        else (void)hipGetLastError();
+        read_timing_slot(actx, prof);
     }
     return ACGPU_OK;
 }
@@ -196,15 +193,9 @@ acgpu_status nonoverlapping_core(acgpu_automaton* occ, DeviceState* ds, Scratch*
         const bool few = m_total <= kSelectFewLimit;   // (no scan launches: the stream length stays in d_tot until the last kernel)
         if (!few) HIP_TRY(hipMemcpyAsync(sc->seltot.p, d_tot, sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));  // n_in survives the scan below
         const uint64_t nblk = (m_total + 1023) / 1024;
-        HIP_TRY(sc->counts.ensure(nblk * sizeof(uint32_t) + 16));
-        HIP_TRY(sc->offsets.ensure(nblk * sizeof(uint64_t)));
-        HIP_TRY(sc->active.ensure(nblk * sizeof(uint64_t)));
-        HIP_TRY(sc->aoff.ensure(nblk * sizeof(uint64_t)));
-        HIP_TRY(sc->bsum.ensure(((nblk + 255) / 256 + 1) * sizeof(uint64_t)));
-        HIP_TRY(sc->bact.ensure(((nblk + 255) / 256 + 1) * sizeof(uint32_t)));
+        // (256 blocks of slack: the selection's scan wants 16 bytes behind the counts and one more block sum; ss.totals is d_tot)
         ScanScratch ss;
-        ss.counts = sc->counts.as<uint32_t>(); ss.offsets = sc->offsets.as<uint64_t>(); ss.active = sc->active.as<uint64_t>();
-        ss.aoff = sc->aoff.as<uint64_t>(); ss.bsum = sc->bsum.as<uint64_t>(); ss.bact = sc->bact.as<uint32_t>(); ss.totals = d_tot;
+        if ((st = scan_scratch(sc, nblk + 256, true, &ss))) return st;
         HIP_TRY(launch_select_parallel(dS, m_total, few ? d_tot : sc->seltot.as<uint64_t>(), rule_kind, pos0,
                                        occ->nnfa.max_pattern_len, sc->selwork.p, ss, sel_dst, m_total,
                                        stream));
@@ -262,8 +253,9 @@ acgpu_status nonoverlapping_windowed(acgpu_automaton* aut, const acgpu_input* in
     const uint64_t L = std::max<uint64_t>(occ->nnfa.max_pattern_len, 1);
     const uint64_t w_min = std::max<uint64_t>(4 * L, 4096);
     auto trim = [&]() {
-        for (DevBuf* b : {&sc->result, &sc->sel, &sc->selwork, &sc->events, &sc->eswork})
+        for (DevBuf* b : {&sc->result, &sc->sel, &sc->selwork, &sc->events})
             if (b->bytes > (size_t(1) << 30)) b->release();
+        if (sc->order.buf.bytes > (size_t(1) << 30)) sc->order.release();
     };
     trim();
     uint64_t pos = in->span_start;
@@ -519,7 +511,8 @@ acgpu_status find_parallel(acgpu_automaton* aut, const acgpu_input* in, int rule
             uint64_t n_sel = 0;
             st = nonoverlapping_core(occ, ds, sc.s.get(), in, size_t(lo), size_t(b), in->span_start, rule, &n_sel, nullptr, dense);
             if (st == ACGPU_ERR_NOMEM && !dense->hit && b - a > (uint64_t(64) << 10)) {   // occurrence stream of the window too large
-                for (DevBuf* buf : {&sc->result, &sc->sel, &sc->selwork, &sc->events, &sc->eswork}) buf->release();
+                for (DevBuf* buf : {&sc->result, &sc->sel, &sc->selwork, &sc->events}) buf->release();
+                sc->order.release();
                 w = std::max<uint64_t>((b - a) / 16, uint64_t(64) << 10);
                 b = std::min<uint64_t>(in->span_end, a + w);
                 attempt = -1;

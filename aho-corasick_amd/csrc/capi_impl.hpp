@@ -33,6 +33,7 @@
 #include "host/devbuf.hpp"
 #include "host/engine_plan.hpp"
 #include "host/lw_tables.hpp"
+#include "host/ov_sizes.hpp"
 #include "host/pf_tables.hpp"
 
 namespace acgpu_capi {
@@ -70,11 +71,41 @@ acgpu_status hip_fail(hipError_t e, const char* what);
         if (e_ != hipSuccess) return hip_fail(e_, #expr);     \
     } while (0)
 
+// Work area of the bucket order pass (event_order.hip) and what is known about its leading bucket words.  The fused chain
+// wants them zero when its scan starts and re-zeroes them BEHIND its last kernel, so that the next call on the stream
+// finds them so: `known_zero` bytes are zero, or will be when the stream gets there.
+struct OrderWork {
+    DevBuf buf;
+    size_t known_zero = 0;
+    // at least n bytes; a new allocation has undefined contents, whatever its address
+    hipError_t reserve(size_t n) {
+        const size_t had = buf.bytes;
+        const hipError_t e = buf.ensure(n);
+        if (buf.bytes != had) known_zero = 0;
+        return e;
+    }
+    // the first zb bytes are zero when the work queued on `s` so far has run; they count as dirty from here on
+    hipError_t zero(size_t zb, hipStream_t s) {
+        const bool known = known_zero && known_zero >= zb;
+        known_zero = 0;
+        return known ? hipSuccess : hipMemsetAsync(buf.p, 0, zb, s);
+    }
+    // queues the re-zeroing of the first zb bytes behind the work on `s` and remembers it
+    hipError_t rezero_behind(size_t zb, hipStream_t s) {
+        const hipError_t e = launch_event_order_zero(buf.p, zb, s);
+        known_zero = e == hipSuccess ? zb : 0;
+        return e;
+    }
+    void dirty() { known_zero = 0; }   // (any other use of the area, or a failed call)
+    void release() { buf.release(); known_zero = 0; }
+};
+
 // One scan's worth of scratch; pooled per device so concurrent searches do not share state.
 struct Scratch {
     DevBuf counts, offsets, active, aoff, bsum, bact, totals, result, hay, sel, selwork, seltot;
     DevBuf rhay, rmatch, rtab, roff, rwork, rout;  // replace_all
-    DevBuf events, evrank, evctr, eswork;          // prefix-filter direct / sorted-events modes (level-3 events -> ordered records)
+    DevBuf events, evrank, evctr;                  // prefix-filter direct / sorted-events modes (level-3 events -> ordered records)
+    OrderWork order;                               // ... and the order pass's work area
     DevBuf hitwork;                                // large-set filter: global hit list of its second-pass level 3
     DevBuf triev, triseg, trictr;                  // contiguous-NFA walk: match events of the count pass (cnfa_tri.hip)
     DevBuf lwev, lwtn, lwovf;                      // LDS walk: match events of the count walk by task, their counts, the overflow word (lds_emit.hip)
@@ -83,10 +114,6 @@ struct Scratch {
     bool probe_ready = false;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool ev_armed = false;        // evrank[] == 0 and evctr[] == 0 (the invariant k_ev_write restores; false after a failed call)
-    // fused order chain (event_order.hip): the first eo_zero_bytes of eswork at eo_zero_p are zero (or will be when the stream
-    // gets there: the chain re-zeroes them BEHIND its last kernel); nullptr after any other use of eswork or a failed call
-    void* eo_zero_p = nullptr;
-    size_t eo_zero_bytes = 0;
     bool events_served = false;   // the last internal-mode search on this scratch took its records from the prefix filter's events
     bool rank_over = false;       // ... which had more events than the all-pairs rank takes
     uint32_t rank_hint = 0;       // events of the previous event-mode call on this scratch: sizes the all-pairs grid only
@@ -126,9 +153,8 @@ struct EnqueueGuess {
     // out: the bound the order pass was queued with.  totals[1] is NOT reset by the pass in this form (one launch less): the
     // records are there iff totals[1] <= served_events and totals[0] <= cap
     uint64_t served_events = 0;
-    // out: the fused order chain was queued (event_order.hip): totals = {records, 0 = delivered | UINT64_MAX}, and the caller
-    // launches launch_event_order_zero(rearm_p, rearm_bytes) BEHIND its own kernels (then marks the scratch: Scratch::eo_zero_p)
-    void* rearm_p = nullptr;
+    // out: != 0: the fused order chain was queued (event_order.hip): totals = {records, 0 = delivered | UINT64_MAX}, and the
+    // caller queues OrderWork::rezero_behind(rearm_bytes) on the stream's scratch BEHIND its own kernels
     size_t rearm_bytes = 0;
 };
 
@@ -306,16 +332,34 @@ acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_
 uint32_t default_chunk(const acgpu_automaton* aut, size_t span_len);
 // scan geometry of one shard: 64-byte aligned base, ownership window, chunk grid
 ScanGeom make_geom(const acgpu_automaton* aut, const acgpu_input* in, size_t shard_begin, size_t shard_end, const uint8_t* dhay, size_t halo);
+ScanGeom with_chunk(ScanGeom g, uint32_t chunk);   // the same window on a grid of `chunk` bytes (the LDS walk's lane-chunks)
 // ---- capi_overlap.cpp (shared with the enqueue-only form, capi_enqueue.cpp)
 constexpr uint32_t ENG_PF_LARGE = 100;                   // pf_alternative only: the prefix filter's other kernel (reported as ENG_PF)
-constexpr uint32_t kEvAllPairs = 16384;                  // events the all-pairs rank orders (k_ev_rank)
-constexpr uint64_t kSortMaxEvents = uint64_t(12) << 20;  // events the bucket order pass takes (event_order.hip)
 constexpr uint64_t kProbeMinSpan = uint64_t(16) << 20;   // shards below this pay less for an abandoned pass than a probe is worth
 acgpu_status pf_route_prepare(Scratch* sc, const HotTables& h, uint64_t span_bytes, PfRoute* r);
-acgpu_status ensure_order_work(Scratch* sc, size_t bytes, hipStream_t);
+// the common prefix of the argument checks of every form of the overlapping search, in the reference's order
+// (automaton.rs:397-423); *target: the automaton that serves the call (StartKind::Both: the unanchored twin)
+acgpu_status check_overlapping(acgpu_automaton* aut, const acgpu_input* in, acgpu_automaton** target);
+// the scan's buffers for n_chunks chunks (`offsets` only where a kernel looks up every chunk's output offset)
+acgpu_status scan_scratch(Scratch* sc, uint64_t n_chunks, bool with_offsets, ScanScratch* ss);
+// the prefix filter's event list for cap_ev events, its counters and rank words armed on `stream`
+acgpu_status arm_pf_events(Scratch* sc, uint64_t cap_ev, hipStream_t stream, unsigned long long** ctr, uint32_t** rank);
+// the filter scan into the event list and, when the device-side probe was queued (route.gate), the gated other filter
+acgpu_status launch_pf_scan_pair(Scratch* sc, const HotTables& h, const ScanGeom& g, uint64_t span_bytes, unsigned long long* ctr,
+                                 uint64_t cap_ev, PfRoute route, bool probe, hipStream_t stream);
+// the fill kernel behind count -> scan for count engine `eng` (records from the tri-walk's events when `tev` has them)
+hipError_t launch_fill(const acgpu_automaton* aut, const DeviceState* ds, uint32_t eng, const ScanGeom& g, const ScanScratch& ss,
+                       const TriEvents& tev, bool emit_events, acgpu_match* dst, uint64_t cap, uint64_t max_waves, hipStream_t stream);
+// the LDS walk's event form: its lane-chunk size for this call (0: the form does not apply), and the chunk fill behind
+// overflowed events over lane-chunk geometry g (gate != nullptr: queued blind, runs only if the overflow word holds `gen`)
+uint32_t lw_events_lane_chunk(const acgpu_automaton* aut, const DeviceState* ds, uint32_t eng, const ScanGeom& g);
+hipError_t launch_lw_chunk_fill(const HotTables& h, const ScanGeom& g, const ScanScratch& ss, uint64_t cap, uint64_t max_waves,
+                                acgpu_match* dst, const uint32_t* gate, uint32_t gen, hipStream_t stream);
+// the library's own timing slot of a stream's enqueue context (slot 64) into prof
+void read_timing_slot(DeviceState::AsyncCtx* actx, acgpu_profile* prof);
 acgpu_status ensure_probe(Scratch* sc, hipStream_t stream);
 bool tri_walk_selected(uint32_t eng, const DeviceState* ds);
-acgpu_status cnfa_tri_events(const DeviceState* ds, Scratch* sc, const ScanGeom& g, uint64_t span_bytes, hipStream_t stream, TriEvents* ev);
+acgpu_status cnfa_tri_events(const DeviceState* ds, Scratch* sc, uint32_t eng, const ScanGeom& g, uint64_t span_bytes, hipStream_t stream, TriEvents* ev, ScanScratch* ss);
 hipError_t launch_generic_count(uint32_t eng, DeviceState* ds, const ScanGeom& g, uint32_t* counts, hipStream_t stream, const TriEvents* tev = nullptr);
 uint32_t pf_alternative(const acgpu_automaton* aut, const DeviceState* ds, PfRoute* route);
 // scratch of the LDS walk's event form for geometry g (lds_emit.hip); *gen: the call's value of the overflow word

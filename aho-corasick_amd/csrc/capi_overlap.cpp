@@ -80,9 +80,30 @@ enum class PfOutcome { Done, Abandoned, TooManyEvents };
 // span (one event per 64 haystack bytes, at most kSortMaxEvents), so which of the two runs is decided by the count this
 // very call produced -- no state carried between calls.  Outcomes other than Done leave no result: the scan was
 // abandoned by its routing rule (PfArgs::route_*), or produced more events than the buffer holds.
-// scratch of the bucket order pass (event_order.hip)
-acgpu_status ensure_order_work(Scratch* sc, size_t bytes, hipStream_t) {
-    HIP_TRY(sc->eswork.ensure(bytes));
+acgpu_status arm_pf_events(Scratch* sc, uint64_t cap_ev, hipStream_t stream, unsigned long long** ctr, uint32_t** rank) {
+    // invariant between calls: rank[] == 0 and the counters == 0 (k_ev_write restores it).  A call that fails between
+    // the scan and k_ev_write leaves them dirty; ev_armed says whether the invariant holds (false on a new scratch).
+    HIP_TRY(sc->events.ensure(size_t(cap_ev) * pf_event_bytes()));
+    HIP_TRY(sc->evrank.ensure(size_t(kEvAllPairs) * sizeof(uint32_t)));
+    HIP_TRY(sc->evctr.ensure(kPfCtrWords * sizeof(unsigned long long)));
+    if (!sc->ev_armed) {
+        HIP_TRY(hipMemsetAsync(sc->evrank.p, 0, size_t(kEvAllPairs) * sizeof(uint32_t), stream));
+        HIP_TRY(hipMemsetAsync(sc->evctr.p, 0, kPfCtrWords * sizeof(unsigned long long), stream));
+    }
+    sc->ev_armed = false;
+    *ctr = sc->evctr.as<unsigned long long>();
+    *rank = sc->evrank.as<uint32_t>();
+    return ACGPU_OK;
+}
+acgpu_status launch_pf_scan_pair(Scratch* sc, const HotTables& h, const ScanGeom& g, uint64_t span_bytes, unsigned long long* ctr,
+                                 uint64_t cap_ev, PfRoute route, bool probe, hipStream_t stream) {
+    if (acgpu_status st = pf_route_prepare(sc, h, span_bytes, &route)) return st;
+    HIP_TRY(launch_pf_any(h, g, nullptr, stream, sc->events.p, ctr, cap_ev, route));
+    if (!probe) return ACGPU_OK;
+    PfRoute other;   // (both gated scans carry the histogram, if any: one of them runs)
+    other.force_pfx = true; other.gate = route.gate; other.gate_val = 1; other.hist = route.hist;
+    if (acgpu_status st = pf_route_prepare(sc, h, span_bytes, &other)) return st;
+    HIP_TRY(launch_pf_any(h, g, nullptr, stream, sc->events.p, ctr, cap_ev, other));
     return ACGPU_OK;
 }
 acgpu_status ensure_probe(Scratch* sc, hipStream_t stream) {
@@ -99,19 +120,10 @@ acgpu_status pf_events(OvCtx& c, PfRoute route, PfOutcome* outcome, acgpu_status
     const bool legs = c.prof && !c.dev_result;   // the legs behind the scan are timed (ov_events_ms)
     *outcome = PfOutcome::Done;
     *result = ACGPU_OK;
-    const uint64_t cap_ev = std::min<uint64_t>(kSortMaxEvents, std::max<uint64_t>(uint64_t(1) << 16, c.span_bytes / 64));
-    // invariant between calls: rank[] == 0 and the counters == 0 (k_ev_write restores it).  A call that fails between
-    // the scan and k_ev_write leaves them dirty; ev_armed says whether the invariant holds.
-    HIP_TRY(sc->events.ensure(size_t(cap_ev) * pf_event_bytes()));
-    HIP_TRY(sc->evrank.ensure(size_t(kEvAllPairs) * sizeof(uint32_t)));
-    HIP_TRY(sc->evctr.ensure(kPfCtrWords * sizeof(unsigned long long)));
-    if (!sc->ev_armed) {
-        HIP_TRY(hipMemsetAsync(sc->evrank.p, 0, size_t(kEvAllPairs) * sizeof(uint32_t), stream));
-        HIP_TRY(hipMemsetAsync(sc->evctr.p, 0, kPfCtrWords * sizeof(unsigned long long), stream));
-    }
-    sc->ev_armed = false;
-    unsigned long long* ctr = sc->evctr.as<unsigned long long>();
-    uint32_t* rank = sc->evrank.as<uint32_t>();
+    const uint64_t cap_ev = ov_event_capacity(c.span_bytes);
+    unsigned long long* ctr = nullptr;
+    uint32_t* rank = nullptr;
+    if (acgpu_status st = arm_pf_events(sc, cap_ev, stream, &ctr, &rank)) return st;
     if (acgpu_status st = pf_route_prepare(sc, c.ds->hot, c.span_bytes, &route)) return st;
     if (c.prof) HIP_TRY(hipEventRecord(sc->ev[0], stream));
     HIP_TRY(launch_pf_any(c.ds->hot, c.g, nullptr, stream, sc->events.p, ctr, cap_ev, route));
@@ -143,8 +155,8 @@ acgpu_status pf_events(OvCtx& c, PfRoute route, PfOutcome* outcome, acgpu_status
         if (!all_pairs && !abandoned && n_events <= cap_ev && n_records > 0) {
             zero_bytes = event_order_zero_bytes(n_events, n_records, c.span_bytes);
             if (zero_bytes <= (size_t(1) << 20)) {
-                if (acgpu_status st = ensure_order_work(sc, event_order_work_bytes(n_events, n_records, c.span_bytes), stream)) return st;
-                zero_p = sc->eswork.p; order_zeroed = true;
+                HIP_TRY(sc->order.reserve(event_order_work_bytes(n_events, n_records, c.span_bytes)));
+                zero_p = sc->order.buf.p; order_zeroed = true;
             } else zero_bytes = 0;
         }
         if (legs) HIP_TRY(hipEventRecord(sc->ev[3], stream));
@@ -194,9 +206,9 @@ acgpu_status pf_events(OvCtx& c, PfRoute route, PfOutcome* outcome, acgpu_status
     // (the selection kernels of the parallel find_iter read the record count from the device totals: still there)
     if (legs) HIP_TRY(hipEventRecord(sc->ev[3], stream));
     if (dst && n_events) {
-        if (acgpu_status st = ensure_order_work(sc, event_order_work_bytes(n_events, n_records, c.span_bytes), stream)) return st;
+        HIP_TRY(sc->order.reserve(event_order_work_bytes(n_events, n_records, c.span_bytes)));
         HIP_TRY(launch_event_order_emit(c.ds->hot, c.ds->da, sc->events.p, c.ss.totals, kEvAllPairs, n_events, n_records,
-                                        c.shard_begin, c.span_bytes, sc->eswork.p, dst, stream, nullptr, order_zeroed));
+                                        c.shard_begin, c.span_bytes, sc->order.buf.p, dst, stream, nullptr, order_zeroed));
     }
     if (legs) HIP_TRY(hipEventRecord(sc->ev[4], stream));
     if (dst && !c.to_caller && !c.dev_result)
@@ -206,11 +218,7 @@ acgpu_status pf_events(OvCtx& c, PfRoute route, PfOutcome* outcome, acgpu_status
         // internal mode (find_iter's occurrence stream): the caller continues on this stream -- selection kernels, then its
         // own synchronisation -- so the order pass is not waited for here (one host round trip less per find_iter); only
         // the scan's time, complete since the counts were read, is reported
-        if (c.prof) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, sc->ev[0], sc->ev[1]));
-            c.prof->ms_scan = ms; c.prof->ms_total = ms;
-        }
+        if (acgpu_status st = ov_events_ms(c, false)) return st;
         *result = ov_result(c, n_records, dst);
         return ACGPU_OK;
     }
@@ -234,11 +242,13 @@ bool dfa_tri_selected(const DeviceState* ds) {
 bool tri_walk_selected(uint32_t eng, const DeviceState* ds) {
     return (eng == ENG_CNFA && cnfa_tri_selected(ds)) || (eng == ENG_DFA && dfa_tri_selected(ds));
 }
-// Event buffer for a scan by that kernel (zeroed counters enqueued on `stream`): the count pass then records every
-// match state it enters, and k_cnfa_tri_emit writes the ordered records without walking the haystack again.
-acgpu_status cnfa_tri_events(const DeviceState* ds, Scratch* sc, const ScanGeom& g, uint64_t span_bytes, hipStream_t stream, TriEvents* ev) {
+// Event buffer for a scan by that kernel, if `eng` runs it (zeroed counters enqueued on `stream`): the count pass then records
+// every match state it enters, and k_cnfa_tri_emit writes the ordered records without walking the haystack again.
+acgpu_status cnfa_tri_events(const DeviceState* ds, Scratch* sc, uint32_t eng, const ScanGeom& g, uint64_t span_bytes, hipStream_t stream,
+                             TriEvents* ev, ScanScratch* ss) {
     *ev = TriEvents();
-    if (!ds->var.tri_events || g.n_chunks >= 0xFFFFFFFFull) return ACGPU_OK;   // (variant tri_events = 0: count -> scan -> re-walking fill)
+    // (variant tri_events = 0: count -> scan -> re-walking fill)
+    if (!tri_walk_selected(eng, ds) || !ds->var.tri_events || g.n_chunks >= 0xFFFFFFFFull) return ACGPU_OK;
     const uint32_t segs = tri_event_segments(span_bytes);
     HIP_TRY(sc->triev.ensure(size_t(segs) * kTriSeg * sizeof(TriEvent)));
     HIP_TRY(sc->triseg.ensure(size_t(segs) * sizeof(uint32_t)));
@@ -246,7 +256,7 @@ acgpu_status cnfa_tri_events(const DeviceState* ds, Scratch* sc, const ScanGeom&
     HIP_TRY(hipMemsetAsync(sc->trictr.p, 0, 2 * sizeof(unsigned long long), stream));
     ev->ev = sc->triev.as<TriEvent>(); ev->seg_fill = sc->triseg.as<uint32_t>();
     ev->ctr = sc->trictr.as<unsigned long long>(); ev->max_segs = segs;
-    return ACGPU_OK;
+    return scan_scratch(sc, g.n_chunks, true, ss);   // (the emit kernel looks up every chunk's output offset)
 }
 
 hipError_t launch_generic_count(uint32_t eng, DeviceState* ds, const ScanGeom& g, uint32_t* counts, hipStream_t stream,
@@ -256,6 +266,44 @@ hipError_t launch_generic_count(uint32_t eng, DeviceState* ds, const ScanGeom& g
     if (eng == ENG_DFA && dfa_tri_selected(ds)) return launch_dfa_tri_count(ds->dfa_tri, g, counts, tev && tev->ev ? tev : nullptr, stream);
     if (eng == ENG_CNFA && ds->cnfa_hot.ready && !literal) return launch_cnfa_count(ds->cnfa_hot, ds->da, g, counts, stream);
     return launch_walk_count(eng, ds->da, g, counts, stream);
+}
+
+acgpu_status scan_scratch(Scratch* sc, uint64_t n_chunks, bool with_offsets, ScanScratch* ss) {
+    const uint64_t nb = (n_chunks + 255) / 256;
+    HIP_TRY(sc->counts.ensure(n_chunks * sizeof(uint32_t)));
+    if (with_offsets) HIP_TRY(sc->offsets.ensure(n_chunks * sizeof(uint64_t)));
+    HIP_TRY(sc->active.ensure(n_chunks * sizeof(uint64_t)));
+    HIP_TRY(sc->aoff.ensure(n_chunks * sizeof(uint64_t)));
+    HIP_TRY(sc->bsum.ensure(nb * sizeof(uint64_t)));
+    HIP_TRY(sc->bact.ensure(nb * sizeof(uint32_t)));
+    HIP_TRY(sc->totals.ensure(2 * sizeof(uint64_t)));
+    *ss = ScanScratch();
+    ss->counts = sc->counts.as<uint32_t>();
+    ss->offsets = with_offsets ? sc->offsets.as<uint64_t>() : nullptr;   // (a fill only needs the active chunks' offsets)
+    ss->active = sc->active.as<uint64_t>(); ss->aoff = sc->aoff.as<uint64_t>(); ss->bsum = sc->bsum.as<uint64_t>();
+    ss->bact = sc->bact.as<uint32_t>(); ss->totals = sc->totals.as<uint64_t>();
+    return ACGPU_OK;
+}
+
+hipError_t launch_fill(const acgpu_automaton* aut, const DeviceState* ds, uint32_t eng, const ScanGeom& g, const ScanScratch& ss,
+                       const TriEvents& tev, bool emit_events, acgpu_match* dst, uint64_t cap, uint64_t max_waves, hipStream_t stream) {
+    if (tev.ev) {
+        // shallow-skip walks, event form: the emit kernel; the re-walking fill behind it only runs if the events overflowed
+        // (gate).  emit_events = false: the host already knows that they did
+        if (emit_events) {
+            const hipError_t e = eng == ENG_CNFA
+                ? launch_cnfa_tri_emit(ds->cnfa_tri, ds->da.cnfa.plens, g, tev, ss.offsets, ss.totals, cap, dst, stream)
+                : launch_dfa_tri_emit(ds->dfa_tri, ds->da, g, tev, ss.offsets, ss.totals, cap, dst, stream);
+            if (e != hipSuccess) return e;
+        }
+        return launch_walk_fill(eng, ds->da, g, ss.active, ss.totals, cap, max_waves, ss.aoff, dst, stream, tev.ctr + 1);
+    }
+    const uint32_t fill_eng = generic_engine(aut, ds);
+    const bool lds_ok = fill_eng == ENG_DFA && aut->cfg.engine != 1;   // (an explicitly requested transition walk keeps its own fill)
+    // small automata: the fill whose walk AND match lists live in LDS
+    if (lds_ok && lw_fill_supported(ds->hot)) return launch_lw_fill(ds->hot, g, ss.active, ss.totals, cap, max_waves, ss.aoff, dst, stream);
+    if (lds_ok && hot_fill_supported(ds->hot, g)) return launch_hot_fill(ds->hot, ds->da, g, ss.active, ss.totals, cap, max_waves, ss.aoff, dst, stream);
+    return launch_walk_fill(fill_eng, ds->da, g, ss.active, ss.totals, cap, max_waves, ss.aoff, dst, stream);
 }
 
 // Classic pipeline, any count engine: per-chunk counts -> scan + compaction -> fill of the non-empty chunks by the
@@ -270,13 +318,7 @@ acgpu_status classic_pipeline(OvCtx& c, uint32_t eng) {
     pfr.force_pfx = c.force_large_set;
     if (eng == ENG_PF) if (acgpu_status st = pf_route_prepare(sc, ds->hot, c.span_bytes, &pfr)) return st;
     TriEvents tev;   // shallow-skip walks: records from the count pass's events (no second walk)
-    if (tri_walk_selected(eng, ds)) {
-        if (acgpu_status st = cnfa_tri_events(ds, sc, g, c.span_bytes, stream, &tev)) return st;
-        if (tev.ev) {   // the emit kernel looks up every chunk's output offset
-            HIP_TRY(sc->offsets.ensure(g.n_chunks * sizeof(uint64_t)));
-            c.ss.offsets = sc->offsets.as<uint64_t>();
-        }
-    }
+    if (acgpu_status st = cnfa_tri_events(ds, sc, eng, g, c.span_bytes, stream, &tev, &c.ss)) return st;
     if (c.prof) HIP_TRY(hipEventRecord(sc->ev[0], stream));
     if (eng == ENG_PF) HIP_TRY(launch_pf_any(ds->hot, g, c.ss.counts, stream, nullptr, nullptr, 0, pfr));
     else if (eng == ENG_HOT) HIP_TRY(launch_hot_count(ds->hot, ds->da, g, c.ss.counts, stream));
@@ -284,31 +326,11 @@ acgpu_status classic_pipeline(OvCtx& c, uint32_t eng) {
     if (c.prof) HIP_TRY(hipEventRecord(sc->ev[1], stream));
     HIP_TRY(launch_scan(c.ss, g.n_chunks, stream));
     if (c.prof) HIP_TRY(hipEventRecord(sc->ev[2], stream));
-    const uint32_t fill_eng = generic_engine(aut, ds);
-    const bool hot_fill = fill_eng == ENG_DFA && aut->cfg.engine != 1 && hot_fill_supported(ds->hot, g);
-    // small automata: the fill whose walk AND match lists live in LDS (an explicitly requested transition walk keeps its own)
-    const bool lw_fill = fill_eng == ENG_DFA && aut->cfg.engine != 1 && lw_fill_supported(ds->hot);
-    bool events_ok = tev.ev != nullptr;   // (host path: cleared below when the buffer overflowed)
-    auto fill = [&](uint64_t fcap, uint64_t max_waves, acgpu_match* dst) -> hipError_t {
-        if (tev.ev) {
-            // event form: the emit kernel; the re-walking fill behind it only runs if the events overflowed (gate)
-            if (events_ok) {
-                const hipError_t e = eng == ENG_CNFA
-                    ? launch_cnfa_tri_emit(ds->cnfa_tri, ds->da.cnfa.plens, g, tev, c.ss.offsets, c.ss.totals, fcap, dst, stream)
-                    : launch_dfa_tri_emit(ds->dfa_tri, ds->da, g, tev, c.ss.offsets, c.ss.totals, fcap, dst, stream);
-                if (e != hipSuccess) return e;
-            }
-            return launch_walk_fill(eng, ds->da, g, c.ss.active, c.ss.totals, fcap, max_waves, c.ss.aoff, dst, stream, tev.ctr + 1);
-        }
-        if (lw_fill) return launch_lw_fill(ds->hot, g, c.ss.active, c.ss.totals, fcap, max_waves, c.ss.aoff, dst, stream);
-        if (hot_fill) return launch_hot_fill(ds->hot, ds->da, g, c.ss.active, c.ss.totals, fcap, max_waves, c.ss.aoff, dst, stream);
-        return launch_walk_fill(fill_eng, ds->da, g, c.ss.active, c.ss.totals, fcap, max_waves, c.ss.aoff, dst, stream);
-    };
     if (c.to_caller) {
         // Device-resident output: the fill kernel reads the totals on the device, so it is enqueued right behind
         // the scan without a host round trip; it writes nothing if the records would not fit into `cap`.
         if (c.prof) HIP_TRY(hipEventRecord(sc->ev[3], stream));
-        if (c.cap > 0 && c.out) HIP_TRY(fill(c.cap, 16384, c.out));
+        if (c.cap > 0 && c.out) HIP_TRY(launch_fill(aut, ds, eng, g, c.ss, tev, true, c.out, c.cap, 16384, stream));
         if (c.prof) HIP_TRY(hipEventRecord(sc->ev[4], stream));
     }
     HIP_TRY(sc->ensure_pinned());
@@ -316,7 +338,7 @@ acgpu_status classic_pipeline(OvCtx& c, uint32_t eng) {
     if (tev.ev) HIP_TRY(hipMemcpyAsync(sc->pinned + 2, tev.ctr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     const uint64_t n_records = sc->pinned[0], n_active = sc->pinned[1];
-    if (tev.ev && sc->pinned[3] != 0) events_ok = false;   // more events than the buffer holds: the re-walking fill alone
+    const bool events_ok = !(tev.ev && sc->pinned[3] != 0);   // more events than the buffer holds: the re-walking fill alone
     *c.n_out = size_t(n_records);
     ov_profile(c, eng, n_records, n_active);
     if (c.prof) {
@@ -338,7 +360,7 @@ acgpu_status classic_pipeline(OvCtx& c, uint32_t eng) {
     HIP_TRY(sc->result.ensure(n_records * sizeof(acgpu_match)));
     acgpu_match* dout = sc->result.as<acgpu_match>();
     if (c.prof) HIP_TRY(hipEventRecord(sc->ev[3], stream));
-    HIP_TRY(fill(n_records, n_active, dout));
+    HIP_TRY(launch_fill(aut, ds, eng, g, c.ss, tev, events_ok, dout, n_records, n_active, stream));
     if (c.prof) HIP_TRY(hipEventRecord(sc->ev[4], stream));
     if (c.dev_result) *c.dev_result = dout;  // records stay in scratch->result; the caller continues on the same stream
     else HIP_TRY(hipMemcpyAsync(c.out, dout, n_records * sizeof(acgpu_match), hipMemcpyDeviceToHost, stream));
@@ -369,33 +391,32 @@ acgpu_status ensure_lw_events(Scratch* sc, const ScanGeom& g, hipStream_t stream
     return ACGPU_OK;
 }
 
-// the chunk fill behind an overflowed event form: chunks of four lane-chunks (2 KiB: a wavefront per 512 bytes spends its time
-// on warm-ups and prefix sums -- 1.5 ms against 1.2 for 92 M records), record offsets from the lane-chunk scan
-ScanGeom lw_fill_geom(const ScanGeom& g) {
+// the lane-chunk size of the event form for this call, 0 when the form does not apply
+uint32_t lw_events_lane_chunk(const acgpu_automaton* aut, const DeviceState* ds, uint32_t eng, const ScanGeom& g) {
+    const uint64_t span_bytes = g.emit_hi - g.emit_lo;
+    if (!ov_lw_events_eligible(eng == ENG_HOT, ds->var.lw_events != 0, aut->nnfa.min_pattern_len, span_bytes)) return 0;
+    return lw_events_chunk(ds->hot, g.halo, span_bytes);
+}
+// the chunk fill behind an overflowed event form: the lane-chunk scan (record offsets of the lane-chunks), then chunks of four
+// lane-chunks (kLwFillStride).  gate: the fill runs only if the overflow word holds `gen`; nullptr: the host has seen the
+// overflow
+hipError_t launch_lw_chunk_fill(const HotTables& h, const ScanGeom& g, const ScanScratch& ss, uint64_t cap, uint64_t max_waves,
+                                acgpu_match* dst, const uint32_t* gate, uint32_t gen, hipStream_t stream) {
     ScanGeom f = g;
-    f.chunk = 4 * g.chunk;
-    f.n_chunks = (g.n_chunks + 3) / 4;
-    return f;
+    f.chunk = kLwFillStride * g.chunk;
+    f.n_chunks = ov_lw_fill_chunks(g.n_chunks);
+    const hipError_t e = launch_scan(ss, g.n_chunks, stream);
+    if (e != hipSuccess) return e;
+    return launch_lw_fill(h, f, nullptr, ss.totals, cap, max_waves, nullptr, dst, stream, gate, gen, ss.offsets, kLwFillStride, g.n_chunks);
 }
 
 acgpu_status lw_event_pipeline(OvCtx& c, uint32_t lane_chunk) {
     Scratch* sc = c.sc;
     hipStream_t stream = c.stream;
     DeviceState* ds = c.ds;
-    ScanGeom g = c.g;
-    g.chunk = lane_chunk;
-    g.grid0 = (g.emit_lo / g.chunk) * g.chunk;
-    g.n_chunks = std::max<uint64_t>(1, (g.emit_hi - g.grid0 + g.chunk - 1) / g.chunk);
-    const uint64_t nb = (g.n_chunks + 255) / 256;
-    HIP_TRY(sc->counts.ensure(g.n_chunks * sizeof(uint32_t)));
-    HIP_TRY(sc->offsets.ensure(g.n_chunks * sizeof(uint64_t)));
-    HIP_TRY(sc->active.ensure(g.n_chunks * sizeof(uint64_t)));
-    HIP_TRY(sc->aoff.ensure(g.n_chunks * sizeof(uint64_t)));
-    HIP_TRY(sc->bsum.ensure(nb * sizeof(uint64_t)));
-    HIP_TRY(sc->bact.ensure(nb * sizeof(uint32_t)));
-    ScanScratch ss = c.ss;
-    ss.counts = sc->counts.as<uint32_t>(); ss.offsets = sc->offsets.as<uint64_t>(); ss.active = sc->active.as<uint64_t>();
-    ss.aoff = sc->aoff.as<uint64_t>(); ss.bsum = sc->bsum.as<uint64_t>(); ss.bact = sc->bact.as<uint32_t>();
+    const ScanGeom g = with_chunk(c.g, lane_chunk);
+    ScanScratch ss;
+    if (acgpu_status st = scan_scratch(sc, g.n_chunks, true, &ss)) return st;
     uint32_t gen = 0;
     if (acgpu_status st = ensure_lw_events(sc, g, stream, &gen)) return st;
     uint32_t* ovf = sc->lwovf.as<uint32_t>();
@@ -410,17 +431,12 @@ acgpu_status lw_event_pipeline(OvCtx& c, uint32_t lane_chunk) {
     const bool legs = c.prof && !c.dev_result;
     const bool queued = c.to_caller && c.cap > 0 && c.out;
     bool fill_queued = false;
-    auto chunk_fill = [&](uint64_t fcap, uint64_t max_waves, acgpu_match* dst, const uint32_t* gate) -> acgpu_status {
-        HIP_TRY(launch_scan(ss, g.n_chunks, stream));   // (record offsets of the lane-chunks)
-        HIP_TRY(launch_lw_fill(ds->hot, lw_fill_geom(g), nullptr, ss.totals, fcap, max_waves, nullptr, dst, stream, gate, gen, ss.offsets, 4, g.n_chunks));
-        return ACGPU_OK;
-    };
     if (queued) {   // device-resident output: queued behind the scan, sizes read on the device
         HIP_TRY(launch_lw_ev_emit(ds->hot, g, sc->lwev.p, task_n, ovf, gen, ss.counts, ss.totals, c.cap, c.out, stream));
         // ... and the chunk fill, gated on the overflow word, while recent calls of this automaton overflowed (launches that
         // return at once otherwise; without the hint an overflow costs a host round trip before the fill)
         if (ds->lw_dense_hint.load() > 0) {
-            if (acgpu_status st = chunk_fill(c.cap, 16384, c.out, ovf)) return st;
+            HIP_TRY(launch_lw_chunk_fill(ds->hot, g, ss, c.cap, 16384, c.out, ovf, gen, stream));
             fill_queued = true;
         }
         if (legs) HIP_TRY(hipEventRecord(sc->ev[4], stream));
@@ -444,7 +460,7 @@ acgpu_status lw_event_pipeline(OvCtx& c, uint32_t lane_chunk) {
     if (n_records == 0) return ACGPU_OK;
     if (c.to_caller) {
         if (overflow && c.out && !fill_queued) {   // a slab overflowed: nothing was written, the chunk fill does it now
-            if (acgpu_status st = chunk_fill(c.cap, (g.n_chunks + 3) / 4, c.out, nullptr)) return st;
+            HIP_TRY(launch_lw_chunk_fill(ds->hot, g, ss, c.cap, ov_lw_fill_chunks(g.n_chunks), c.out, nullptr, gen, stream));
             HIP_TRY(hipStreamSynchronize(stream));
         }
         if (overflow) ds->lw_dense_hint.store(8); else if (fill_queued) ds->lw_dense_hint.fetch_sub(1);
@@ -455,7 +471,7 @@ acgpu_status lw_event_pipeline(OvCtx& c, uint32_t lane_chunk) {
     if (c.dev_result && c.dense->too_dense(n_records, c.span_bytes)) { c.dense->hit = true; return ACGPU_ERR_NOMEM; }
     HIP_TRY(sc->result.ensure(n_records * sizeof(acgpu_match)));
     acgpu_match* dout = sc->result.as<acgpu_match>();
-    if (overflow) { if (acgpu_status st = chunk_fill(n_records, (g.n_chunks + 3) / 4, dout, nullptr)) return st; }
+    if (overflow) HIP_TRY(launch_lw_chunk_fill(ds->hot, g, ss, n_records, ov_lw_fill_chunks(g.n_chunks), dout, nullptr, gen, stream));
     else HIP_TRY(launch_lw_ev_emit(ds->hot, g, sc->lwev.p, task_n, ovf, gen, ss.counts, ss.totals, n_records, dout, stream));
     if (c.dev_result) { *c.dev_result = dout; return ACGPU_OK; }   // (the caller continues on this stream)
     HIP_TRY(hipMemcpyAsync(c.out, dout, n_records * sizeof(acgpu_match), hipMemcpyDeviceToHost, stream));
@@ -502,7 +518,7 @@ acgpu_status overlapping_split(acgpu_automaton* aut, const acgpu_input* in, size
     acgpu_input oin = *in;
     oin.out_on_device = 0;
     if (!in->haystack_on_device) {   // one copy of a host haystack for both parts
-        const size_t halo = aut->nnfa.max_pattern_len > 0 ? aut->nnfa.max_pattern_len - 1 : 0;
+        const size_t halo = ov_halo(aut->nnfa.max_pattern_len);
         const size_t need_lo = std::max(in->span_start, shard_begin >= halo ? shard_begin - halo : size_t(0));
         const uint8_t* dhay = nullptr;
         if ((st = device_haystack(in, need_lo, shard_end, sc[0], stream, &dhay))) return st;
@@ -570,14 +586,7 @@ acgpu_status overlapping_split(acgpu_automaton* aut, const acgpu_input* in, size
     return ACGPU_OK;
 }
 
-// `ext` / `dev_result`: internal mode used by the parallel find_iter -- run on the caller's scratch and leave the
-// ordered records in scratch->result (returned through *dev_result) instead of copying them anywhere.
-acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_t shard_begin, size_t shard_end,
-                              acgpu_match* out, size_t cap, size_t* n_out, acgpu_profile* prof,
-                              Scratch* ext, acgpu_match** dev_result, DenseRule* dense) {
-    if (!aut || !n_out) return ACGPU_ERR_INVALID_ARGUMENT;
-    *n_out = 0;
-    if (prof) std::memset(prof, 0, sizeof *prof);
+acgpu_status check_overlapping(acgpu_automaton* aut, const acgpu_input* in, acgpu_automaton** target) {
     acgpu_status st = check_input(in);
     if (st) return st;
     const bool anchored = in->anchored != 0;
@@ -586,18 +595,99 @@ acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_
     if (aut->cfg.match_kind != ACGPU_MATCH_STANDARD) return ACGPU_ERR_UNSUPPORTED_OVERLAPPING;
     if (anchored) return ACGPU_ERR_INVALID_INPUT_ANCHORED;
     if ((st = check_start(aut, false))) return st;
-    if (in->span_start > in->span_end) return ACGPU_OK;  // Input::is_done
-    if (!(in->span_start <= shard_begin && shard_begin <= shard_end && shard_end <= in->span_end))
-        return ACGPU_ERR_INVALID_ARGUMENT;
-
     // StartKind::Both: the unanchored side is served by the twin automaton built with an unanchored start (the same
     // noncontiguous NFA, hence the same match lists in the same order), to which the LDS engines apply; the
     // interleaved two-start DFA layout (dfa.rs:617-724) itself only has the reference-faithful walk
-    if (aut->cfg.start_kind == ACGPU_START_BOTH && aut->occ)
-        return overlapping_impl(aut->occ.get(), in, shard_begin, shard_end, out, cap, n_out, prof, ext, dev_result, dense);
+    *target = aut->cfg.start_kind == ACGPU_START_BOTH && aut->occ ? aut->occ.get() : aut;
+    return ACGPU_OK;
+}
 
+void note_probe_outcome(DeviceState* ds, bool chose_alternative) {
+    if (!chose_alternative) { ds->probe_away_run.store(0, std::memory_order_relaxed); return; }
+    if (ds->probe_away_run.fetch_add(1, std::memory_order_relaxed) + 1 >= 4) {
+        ds->probe_away_run.store(0, std::memory_order_relaxed);
+        ds->probe_skip.store(32, std::memory_order_relaxed);
+    }
+}
+
+void read_timing_slot(DeviceState::AsyncCtx* actx, acgpu_profile* prof) {
+    if (!prof) return;
+    float ms = 0;
+    if (actx->ev[128] && actx->ev[129] && hipEventElapsedTime(&ms, actx->ev[128], actx->ev[129]) == hipSuccess) { prof->ms_scan = ms; prof->ms_total = ms; }
+    else (void)hipGetLastError();
+}
+
+// Device-resident haystack and output, results dense lately: the enqueue-only machinery (probe or sticky choice, gated
+// filters, all-pairs rank AND the bucket order pass, all queued without a host decision) followed by ONE synchronisation,
+// instead of scan -> read the counts -> order pass -> synchronise (natural text, 1 GiB: 0.86 -> 0.79 ms per call).  A call
+// it does not deliver (abandoned scan, more events than the list holds, buffer too small for the order pass) leaves
+// *delivered false: the regular path serves it.
+acgpu_status borrowed_enqueue(OvCtx& c, bool* delivered) {
+    *delivered = false;
+    DeviceState* ds = c.ds;
+    Scratch* sc = c.sc;
+    // (the stream's enqueue context is borrowed for the call; another host thread searching on the same stream at this
+    // moment keeps the regular path and its pooled scratch)
+    DeviceState::AsyncCtx* actx = ds->async_ctx(c.stream);
+    std::unique_lock<std::mutex> borrowed(actx->busy, std::try_to_lock);
+    if (!borrowed.owns_lock()) return ACGPU_OK;
+    const bool was_sticky = ds->probe_skip.load(std::memory_order_relaxed) > 0;
+    bool probed = false;
+    HIP_TRY(sc->ensure_pinned());
+    EnqueueSync sync;
+    sync.host_totals = sc->pinned;
+    sync.seq = ++sc->fin_seq;
+    if (acgpu_status st = enqueue_impl(c.aut, c.in, c.shard_begin, c.shard_end, c.out, c.cap, c.ss.totals, 64, 0, &probed, nullptr, &sync)) return st;
+    // fused order chain (sync.done): its last kernel stored {records, 0 = delivered, events} in the page-locked words; the
+    // launch behind it, which re-zeroes the bucket words for the next call, is not waited for.  Otherwise {records, events}
+    // are copied back
+    const bool by_chain = sync.done != nullptr;
+    if (!by_chain) HIP_TRY(hipMemcpyAsync(sc->pinned, c.ss.totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
+    if (probed)   // what the device-side probe of THIS call decided (a call without a probe leaves an older word there)
+        HIP_TRY(hipMemcpyAsync(sc->pinned + 4, actx->sc.probe.as<uint8_t>() + 64, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+    if (probed || !by_chain) HIP_TRY(hipStreamSynchronize(c.stream));
+    else {
+        // the chain's last kernel stores the call's sequence number behind the totals: polled here (the event behind
+        // that kernel costs the stream ~6 us more before the host hears of it); the event is the fallback
+        const volatile uint64_t* seen = sc->pinned + 3;
+        bool done = false;
+        for (uint32_t spins = 0; spins < (1u << 22) && !(done = *seen == sync.seq); spins++) __builtin_ia32_pause();
+        if (done) std::atomic_thread_fence(std::memory_order_acquire);
+        else HIP_TRY(hipEventSynchronize(sync.done));
+    }
+    if (probed && !was_sticky) note_probe_outcome(ds, (sc->pinned[4] & 0xFFFFFFFFull) != 0);
+    const uint64_t t0 = sc->pinned[0], t1 = sc->pinned[1];
+    if (t0 > c.cap || (by_chain ? t1 != 0 : t1 > ACGPU_ENQUEUE_MAX_EVENTS)) {   // not delivered
+        if (by_chain) HIP_TRY(hipStreamSynchronize(c.stream));
+        return ACGPU_OK;
+    }
+    if (t1 == 0 && t0 > 0) ds->dense_hint.store(16, std::memory_order_relaxed);   // delivered by the order pass: still dense
+    *c.n_out = size_t(t0);
+    ov_profile(c, ENG_PF, t0, by_chain ? sc->pinned[2] : t1);
+    read_timing_slot(actx, c.prof);
+    *delivered = true;
+    return ACGPU_OK;
+}
+
+// `ext` / `dev_result`: internal mode used by the parallel find_iter -- run on the caller's scratch and leave the
+// ordered records in scratch->result (returned through *dev_result) instead of copying them anywhere.
+acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_t shard_begin, size_t shard_end,
+                              acgpu_match* out, size_t cap, size_t* n_out, acgpu_profile* prof,
+                              Scratch* ext, acgpu_match** dev_result, DenseRule* dense) {
+    // ---- checks
+    if (!aut || !n_out) return ACGPU_ERR_INVALID_ARGUMENT;
+    *n_out = 0;
+    if (prof) std::memset(prof, 0, sizeof *prof);
+    acgpu_automaton* target = nullptr;
+    acgpu_status st = check_overlapping(aut, in, &target);
+    if (st) return st;
+    if (in->span_start > in->span_end) return ACGPU_OK;  // Input::is_done
+    if (!(in->span_start <= shard_begin && shard_begin <= shard_end && shard_end <= in->span_end))
+        return ACGPU_ERR_INVALID_ARGUMENT;
+    if (target != aut) return overlapping_impl(target, in, shard_begin, shard_end, out, cap, n_out, prof, ext, dev_result, dense);
     if (aut->part[0]) return overlapping_split(aut, in, shard_begin, shard_end, out, cap, n_out, prof, ext, dev_result, dense);
 
+    // ---- context
     DeviceState* ds = nullptr;
     if ((st = get_device_state(aut, &ds))) return st;
     std::unique_ptr<ScratchLease> lease;
@@ -613,25 +703,15 @@ acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_
     c.to_caller = in->out_on_device && !dev_result;
     Scratch* sc = c.sc;
     if (prof && (st = ensure_events(sc))) return st;
-
-    const size_t halo = aut->nnfa.max_pattern_len > 0 ? aut->nnfa.max_pattern_len - 1 : 0;
-    if (halo > 0xFFFFFF00ull) return ACGPU_ERR_INVALID_ARGUMENT;
+    const size_t halo = ov_halo(aut->nnfa.max_pattern_len);
+    if (!ov_halo_ok(halo)) return ACGPU_ERR_INVALID_ARGUMENT;
     const size_t need_lo = std::max(in->span_start, shard_begin >= halo ? shard_begin - halo : size_t(0));
     const uint8_t* dhay = nullptr;
     if ((st = device_haystack(in, need_lo, shard_end, sc, c.stream, &dhay))) return st;
     c.g = make_geom(aut, in, shard_begin, shard_end, dhay, halo);
+    if ((st = scan_scratch(sc, c.g.n_chunks, false, &c.ss))) return st;
 
-    const uint64_t nb = (c.g.n_chunks + 255) / 256;
-    HIP_TRY(sc->counts.ensure(c.g.n_chunks * sizeof(uint32_t)));
-    HIP_TRY(sc->active.ensure(c.g.n_chunks * sizeof(uint64_t)));
-    HIP_TRY(sc->aoff.ensure(c.g.n_chunks * sizeof(uint64_t)));
-    HIP_TRY(sc->bsum.ensure(nb * sizeof(uint64_t)));
-    HIP_TRY(sc->bact.ensure(nb * sizeof(uint32_t)));
-    HIP_TRY(sc->totals.ensure(2 * sizeof(uint64_t)));
-    c.ss.counts = sc->counts.as<uint32_t>(); c.ss.offsets = nullptr;   // the fill only needs the active chunks' offsets
-    c.ss.active = sc->active.as<uint64_t>(); c.ss.aoff = sc->aoff.as<uint64_t>(); c.ss.bsum = sc->bsum.as<uint64_t>();
-    c.ss.bact = sc->bact.as<uint32_t>(); c.ss.totals = sc->totals.as<uint64_t>();
-
+    // ---- routing
     // engine choice (cfg.engine: 0 auto, 1 walk, 2 LDS walk, 3 prefix filter); auto prefers the fastest engine that is
     // available for this automaton.  All engines produce identical results.
     const int want = aut->cfg.engine;
@@ -640,8 +720,6 @@ acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_
         g_last_error = "requested engine is unavailable for this automaton";
         return ACGPU_ERR_INVALID_ARGUMENT;
     }
-
-    const bool no_events = ds->var.pf_classic != 0;   // variant: chunk counters + scan + fill
     // Occurrence-dense input under the large-set filter (dictionary/english/sorted.txt's 121 111 words of four bytes and more
     // over prose: 0.17 occurrences per byte): every occurrence costs the filter a level-3 walk and an event or a counter
     // atomic -- 31 GB/s for its scan, 3.6 GB/s for the whole call (scripts/split_probe.py) -- while the transition walk
@@ -656,96 +734,19 @@ acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_
         }
         return st;
     }
-    // Device-resident haystack and output, results dense lately: the enqueue-only machinery (probe or sticky choice, gated
-    // filters, all-pairs rank AND the bucket order pass, all queued without a host decision) followed by ONE synchronisation,
-    // instead of scan -> read the counts -> order pass -> synchronise (natural text, 1 GiB: 0.86 -> 0.79 ms per call).  A call
-    // it does not deliver (abandoned scan, more events than the list holds, buffer too small for the order pass) falls
-    // through to the regular path.
-    if (eng == ENG_PF && aut->nnfa.max_pattern_len <= 0xFFFF && !no_events && c.to_caller && !ext && want == 0 && in->haystack_on_device &&
-        out && cap > 0 && ds->dense_hint.load(std::memory_order_relaxed) > 0) {
-      // (the stream's enqueue context is borrowed for the call; another host thread searching on the same stream at this
-      // moment keeps the regular path and its pooled scratch)
-      DeviceState::AsyncCtx* actx = ds->async_ctx(c.stream);
-      std::unique_lock<std::mutex> borrowed(actx->busy, std::try_to_lock);
-      if (borrowed.owns_lock()) {
-        uint64_t* tot = c.ss.totals;
-        const bool was_sticky = ds->probe_skip.load(std::memory_order_relaxed) > 0;
-        bool probed = false;
-        HIP_TRY(sc->ensure_pinned());
-        EnqueueSync sync;
-        sync.host_totals = sc->pinned;
-        sync.seq = ++sc->fin_seq;
-        if ((st = enqueue_impl(aut, in, shard_begin, shard_end, out, cap, tot, 64, 0, &probed, nullptr, &sync))) return st;
-        if (sync.done) {
-            // (fused order chain: its last kernel stored the totals in the page-locked words; the launch behind it, which
-            // re-zeroes the bucket words for the next call, is not waited for)
-            if (probed) {   // (what the device-side probe of THIS call decided: one more word, and the whole stream to wait for)
-                HIP_TRY(hipMemcpyAsync(sc->pinned + 4, actx->sc.probe.as<uint8_t>() + 64, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-                HIP_TRY(hipStreamSynchronize(c.stream));
-                if (!was_sticky) {   // four probes in a row for the large-set filter: the next 32 searches skip the probe
-                    if ((sc->pinned[4] & 0xFFFFFFFFull) != 0) {
-                        if (ds->probe_away_run.fetch_add(1, std::memory_order_relaxed) + 1 >= 4) {
-                            ds->probe_away_run.store(0, std::memory_order_relaxed);
-                            ds->probe_skip.store(32, std::memory_order_relaxed);
-                        }
-                    } else ds->probe_away_run.store(0, std::memory_order_relaxed);
-                }
-            } else {
-                // the chain's last kernel stores the call's sequence number behind the totals: polled here (the event behind
-                // that kernel costs the stream ~6 us more before the host hears of it); the event is the fallback
-                const volatile uint64_t* seen = sc->pinned + 3;
-                bool done = false;
-                for (uint32_t spins = 0; spins < (1u << 22) && !(done = *seen == sync.seq); spins++) __builtin_ia32_pause();
-                if (done) std::atomic_thread_fence(std::memory_order_acquire);
-                else HIP_TRY(hipEventSynchronize(sync.done));
-            }
-            const uint64_t t0 = sc->pinned[0], t1 = sc->pinned[1], n_ev = sc->pinned[2];
-            if (t1 == 0 && t0 <= cap) {
-                if (t0 > 0) ds->dense_hint.store(16, std::memory_order_relaxed);
-                *n_out = size_t(t0);
-                ov_profile(c, ENG_PF, t0, n_ev);
-                if (prof) {
-                    float ms = 0;
-                    if (actx->ev[128] && actx->ev[129] && hipEventElapsedTime(&ms, actx->ev[128], actx->ev[129]) == hipSuccess) { prof->ms_scan = ms; prof->ms_total = ms; }
-                    else (void)hipGetLastError();
-                }
-                return ACGPU_OK;
-            }
-            HIP_TRY(hipStreamSynchronize(c.stream));   // not delivered: the regular path below
-        } else {
-        HIP_TRY(hipMemcpyAsync(sc->pinned, tot, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
-        sc->pinned[2] = 0;
-        if (probed)   // what the device-side probe of THIS call decided (a call without a probe leaves an older word there)
-            HIP_TRY(hipMemcpyAsync(sc->pinned + 2, actx->sc.probe.as<uint8_t>() + 64, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(hipStreamSynchronize(c.stream));
-        if (!was_sticky && probed) {   // four probes in a row for the large-set filter: the next 32 searches skip the probe
-            if ((sc->pinned[2] & 0xFFFFFFFFull) != 0) {
-                if (ds->probe_away_run.fetch_add(1, std::memory_order_relaxed) + 1 >= 4) {
-                    ds->probe_away_run.store(0, std::memory_order_relaxed);
-                    ds->probe_skip.store(32, std::memory_order_relaxed);
-                }
-            } else ds->probe_away_run.store(0, std::memory_order_relaxed);
+    // (variant pf_classic: chunk counters + scan + fill)
+    if (eng == ENG_PF && aut->nnfa.max_pattern_len <= 0xFFFF && !ds->var.pf_classic) {
+        if (c.to_caller && !ext && want == 0 && in->haystack_on_device && out && cap > 0 && ds->dense_hint.load(std::memory_order_relaxed) > 0) {
+            bool delivered = false;
+            if ((st = borrowed_enqueue(c, &delivered))) return st;
+            if (delivered) return ACGPU_OK;
         }
-        const uint64_t t0 = sc->pinned[0], t1 = sc->pinned[1];
-        if (t1 <= ACGPU_ENQUEUE_MAX_EVENTS && t0 <= cap) {   // delivered
-            if (t1 == 0 && t0 > 0) ds->dense_hint.store(16, std::memory_order_relaxed);   // ... by the order pass: still dense
-            *n_out = size_t(t0);
-            ov_profile(c, ENG_PF, t0, t1);
-            if (prof) {
-                float ms = 0;
-                if (actx->ev[128] && actx->ev[129] && hipEventElapsedTime(&ms, actx->ev[128], actx->ev[129]) == hipSuccess) { prof->ms_scan = ms; prof->ms_total = ms; }
-                else (void)hipGetLastError();
-            }
-            return ACGPU_OK;
-        }
-        }
-      }
-    }
-    if (eng == ENG_PF && aut->nnfa.max_pattern_len <= 0xFFFF && !no_events) {
+        // the event form and the routing around it: the probe or the remembered choice in front of the scan, the other
+        // filter or another engine behind a scan that was abandoned
+        acgpu_status result = ACGPU_OK;
         PfRoute route;
         const uint32_t alt = pf_alternative(aut, ds, &route);
         PfOutcome outcome = PfOutcome::Done;
-        acgpu_status result;
         bool probed_away = false;
         EnginePlan plan;
         plan.first = ENG_PF; plan.alternative = alt;
@@ -766,16 +767,9 @@ acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_
             HIP_TRY(hipMemcpyAsync(sc->pinned, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
             HIP_TRY(hipStreamSynchronize(c.stream));
             probed_away = (sc->pinned[0] & 0xFFFFFFFFull) != 0;
-            if (probed_away) {
-                ds->route_hint.store(8, std::memory_order_relaxed);
-                if (ds->probe_away_run.fetch_add(1, std::memory_order_relaxed) + 1 >= 4) {
-                    ds->probe_away_run.store(0, std::memory_order_relaxed);
-                    ds->probe_skip.store(32, std::memory_order_relaxed);
-                }
-            } else {
-                ds->route_hint.fetch_sub(1, std::memory_order_relaxed);
-                ds->probe_away_run.store(0, std::memory_order_relaxed);
-            }
+            if (probed_away) ds->route_hint.store(8, std::memory_order_relaxed);
+            else ds->route_hint.fetch_sub(1, std::memory_order_relaxed);
+            note_probe_outcome(ds, probed_away);
         }
         if (probed_away) outcome = PfOutcome::Abandoned;
         else {
@@ -791,7 +785,7 @@ acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_
             if ((st = pf_events(c, again, &outcome, &result))) return st;
             if (outcome == PfOutcome::Done) return result;
         } else if (outcome == PfOutcome::Abandoned && alt) { eng = alt; c.routed = 1; }
-        // TooManyEvents: the chunk-counter form of the same filter below -- or, for the large-set filter, the walk
+        // TooManyEvents: the chunk-counter form of the same filter -- or, for the large-set filter, the walk
         PfRoute ran;
         ran.force_pfx = c.force_large_set;
         if (outcome == PfOutcome::TooManyEvents && walk_ok && pf_uses_large_set(ds->hot, ran)) {
@@ -800,8 +794,7 @@ acgpu_status overlapping_impl(acgpu_automaton* aut, const acgpu_input* in, size_
             eng = ENG_DFA;
         }
     }
-    if (eng == ENG_HOT && ds->var.lw_events && aut->nnfa.min_pattern_len >= 1 && c.span_bytes < (uint64_t(15) << 30))
-        if (const uint32_t lane_chunk = lw_events_chunk(ds->hot, uint32_t(halo), c.span_bytes)) return lw_event_pipeline(c, lane_chunk);
+    if (const uint32_t lane_chunk = lw_events_lane_chunk(aut, ds, eng, c.g)) return lw_event_pipeline(c, lane_chunk);
     return classic_pipeline(c, eng);
 }
 
@@ -813,7 +806,7 @@ size_t host_piece_bytes() {
 
 // acgpu_find_overlapping* over a HOST haystack that is large enough to be worth pipelining: the span is searched piece
 // by piece (consecutive shards: the concatenation is the full stream by the seam rule), each as soon as its bytes have
-// arrived.  Argument checks in the same order as overlapping_impl.
+// arrived.  The caller has made the argument checks (overlapping_entry: check_overlapping).
 acgpu_status overlapping_host_pipelined(acgpu_automaton* aut, const acgpu_input* in, size_t shard_begin, size_t shard_end,
                                         acgpu_match* out, size_t cap, size_t* n_out, acgpu_profile* prof) {
     *n_out = 0;
@@ -822,7 +815,7 @@ acgpu_status overlapping_host_pipelined(acgpu_automaton* aut, const acgpu_input*
     acgpu_status st = get_device_state(aut, &ds);
     if (st) return st;
     ScratchLease stage(ds);   // holds the device copy of the haystack for the whole call
-    const size_t halo = aut->nnfa.max_pattern_len > 0 ? aut->nnfa.max_pattern_len - 1 : 0;
+    const size_t halo = ov_halo(aut->nnfa.max_pattern_len);
     const size_t need_lo = std::max(in->span_start, shard_begin >= halo ? shard_begin - halo : size_t(0));
     const size_t n = shard_end - need_lo;
     HIP_TRY(stage->hay.ensure(n + 64));
@@ -860,13 +853,12 @@ acgpu_status overlapping_host_pipelined(acgpu_automaton* aut, const acgpu_input*
 // routes a host-haystack / host-output call through the pipelined form when it pays (two pieces or more)
 acgpu_status overlapping_entry(acgpu_automaton* aut, const acgpu_input* in, size_t shard_begin, size_t shard_end,
                                acgpu_match* out, size_t cap, size_t* n_out, acgpu_profile* prof) {
-    if (aut && n_out && in && in->haystack && !in->haystack_on_device && !in->out_on_device && check_input(in) == ACGPU_OK &&
+    acgpu_automaton* target = nullptr;
+    if (aut && n_out && in && in->haystack && !in->haystack_on_device && !in->out_on_device &&
+        check_overlapping(aut, in, &target) == ACGPU_OK &&
         in->span_start <= shard_begin && shard_begin <= shard_end && shard_end <= in->span_end &&
-        shard_end - shard_begin >= 2 * host_piece_bytes() && aut->cfg.match_kind == ACGPU_MATCH_STANDARD && !in->anchored &&
-        enforce_anchored_consistency(aut->cfg.start_kind, false) == ACGPU_OK && check_start(aut, false) == ACGPU_OK) {
-        acgpu_automaton* target = (aut->cfg.start_kind == ACGPU_START_BOTH && aut->occ) ? aut->occ.get() : aut;
+        shard_end - shard_begin >= 2 * host_piece_bytes())
         return overlapping_host_pipelined(target, in, shard_begin, shard_end, out, cap, n_out, prof);
-    }
     return overlapping_impl(aut, in, shard_begin, shard_end, out, cap, n_out, prof);
 }
 

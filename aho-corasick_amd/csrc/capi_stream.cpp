@@ -198,7 +198,7 @@ acgpu_status stream_feed_once(acgpu_stream* s, const uint8_t* bytes, size_t len,
     for (auto& m : s->last) { m.start += base; m.end += base; }
     if (n_sel) s->pos = s->last.back().end;
     // keep the last max_pattern_len-1 bytes as the next chunk's warm-up
-    const size_t want = aut->nnfa.max_pattern_len ? aut->nnfa.max_pattern_len - 1 : 0;
+    const size_t want = ov_halo(aut->nnfa.max_pattern_len);
     const size_t keep = std::min(want, local);
     std::vector<uint8_t> nh(keep);
     if (keep) {

@@ -20,6 +20,7 @@
 #include "host/dfa_tri_tables.hpp"
 #include "host/engine_plan.hpp"
 #include "host/lw_tables.hpp"
+#include "host/ov_sizes.hpp"
 #include "host/pf_tables.hpp"
 
 using namespace acgpu;
@@ -36,7 +37,7 @@ uint64_t run_tri_host(const acgpu_automaton* aut, const uint8_t* haystack, size_
     ScanGeom g{};
     g.hay16 = haystack; g.base_mis = 0; g.cold_floor = 0; g.emit_lo = 0; g.emit_hi = len;
     g.chunk = acgpu_default_chunk(aut, len);
-    g.halo = uint32_t(aut->nnfa.max_pattern_len > 0 ? aut->nnfa.max_pattern_len - 1 : 0);
+    g.halo = uint32_t(ov_halo(aut->nnfa.max_pattern_len));
     g.grid0 = 0;
     g.n_chunks = std::max<uint64_t>(1, (g.emit_hi + g.chunk - 1) / g.chunk);
     g.emit_start_matches = 1;
@@ -171,7 +172,7 @@ acgpu_status acgpu_test_lw_event_records_host(const acgpu_automaton* aut, const 
     LwHostTables t;
     if (!build_lw_host(aut->nnfa, aut->dfa, order, sid2hid, first_match, t, kLwFull, -1)) return ACGPU_OK;
     std::vector<acgpu_match> rec;
-    const uint32_t halo = uint32_t(aut->nnfa.max_pattern_len > 0 ? aut->nnfa.max_pattern_len - 1 : 0);
+    const uint32_t halo = uint32_t(ov_halo(aut->nnfa.max_pattern_len));
     if (!lw_emulate_event_records(t, haystack, len, chunk, halo, rec)) return ACGPU_OK;
     *served = 1;
     *n_out = rec.size();
@@ -192,6 +193,25 @@ acgpu_status acgpu_test_engine_plan(const uint64_t* facts, const int32_t* hints,
     const EnginePlan p = plan_engines(f);
     out[0] = p.first; out[1] = p.alternative;
     out[2] = uint32_t(plan_pf_start(p, hints[0], hints[1], span_bytes, first_kernel_is_large_set != 0));
+    return ACGPU_OK;
+}
+
+// Test hook (NOT a search path): the sizing rules of host/ov_sizes.hpp, which both forms of the overlapping search apply, on explicit integers.
+acgpu_status acgpu_test_ov_sizes(int32_t rule, uint64_t a, uint64_t b, uint64_t c, uint64_t* out) {
+    if (!out) return ACGPU_ERR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = 0;
+    OvOrderBounds ob;
+    switch (rule) {
+        case 0: out[0] = ov_event_capacity(a); return ACGPU_OK;
+        case 1: ob = ov_order_guessed(a, b, c); break;
+        case 2: ob = ov_order_hinted(a, c); break;
+        case 3: out[0] = ov_halo(size_t(a)); out[1] = ov_halo_ok(size_t(out[0])) ? 1 : 0; return ACGPU_OK;
+        case 4: if (c == 0) return ACGPU_ERR_INVALID_ARGUMENT; out[0] = ov_grid_origin(a, uint32_t(c)); out[1] = ov_grid_chunks(a, b, uint32_t(c)); return ACGPU_OK;
+        case 5: out[0] = uint64_t(kLwFillStride) * a; out[1] = ov_lw_fill_chunks(b); return ACGPU_OK;
+        case 6: out[0] = ov_lw_events_eligible((a & 1) != 0, (a & 2) != 0, size_t(b), c) ? 1 : 0; return ACGPU_OK;
+        default: return ACGPU_ERR_INVALID_ARGUMENT;
+    }
+    out[0] = ob.scan_cap; out[1] = ob.events; out[2] = ob.records;
     return ACGPU_OK;
 }
 

@@ -48,6 +48,19 @@ acgpu_status acgpu_test_lw_event_records_host(const acgpu_automaton* aut, const 
 acgpu_status acgpu_test_engine_plan(const uint64_t* facts, const int32_t* hints, uint64_t span_bytes, int32_t first_kernel_is_large_set,
                                     uint32_t* out);
 
+/* Test hook, not a search path: the sizing rules of the overlapping search (aho-corasick_amd/csrc/host/ov_sizes.hpp) on
+ * explicit integers; out: three words.
+ *   rule 0: event-list capacity of a span of `a` bytes -> out[0].
+ *   rules 1 / 2: what a scan over `a` bytes and the order pass queued blind behind it are sized for, with a guessed result
+ *     (b events guessed, room for c records) / with only the density hint (room for c records)
+ *     -> out[0..2] = {capacity the scan is launched with, events, records of the order pass}.
+ *   rule 3: halo of a longest pattern of `a` bytes -> {halo, within the limit}.
+ *   rule 4: chunk grid over [a, b) with chunks of c bytes -> {origin, chunks}.
+ *   rule 5: the chunk fill's grid behind b lane-chunks of `a` bytes -> {chunk bytes, chunks}.
+ *   rule 6: may the LDS walk take its records from its events (a: bit 0 the LDS walk is the engine, bit 1 variant
+ *     lw_events; b: shortest pattern; c: span bytes) -> {0 | 1}. */
+acgpu_status acgpu_test_ov_sizes(int32_t rule, uint64_t a, uint64_t b, uint64_t c, uint64_t* out);
+
 /* Test hook: log2 of the bucket size the event order pass (device/event_order.hip) takes for a scan that may record up to
  * max_events events / max_records records over span_bytes haystack bytes. */
 uint32_t acgpu_test_event_order_shift(uint64_t max_events, uint64_t max_records, uint64_t span_bytes);
