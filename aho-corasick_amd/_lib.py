@@ -4,8 +4,8 @@ import os
 import subprocess
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
-# ACGPU_LIB: kernel-experiment builds of the same library (scripts/pf_variants.sh) or its bounds-checked debug flavour
-# (lib/libacgpu_guard.so, tests/test_gpu_guard.py); never a different backend
+# ACGPU_LIB: another build of the same library, such as its bounds-checked debug flavour (lib/libacgpu_guard.so,
+# tests/test_gpu_guard.py); never a different backend
 _LIB = os.environ.get("ACGPU_LIB") or os.path.join(_PKG, "lib", "libacgpu.so")
 
 

@@ -56,7 +56,7 @@ constexpr size_t kEoLds = size_t(kEoWaves) * 3 * kEoBins * 4;   // per wavefront
 constexpr uint32_t kEoScanBlocks = 1024;          // workgroups of k_eo_scan at most (= published sums)
 constexpr uint32_t kEoScanTile = 2048;            // buckets per tile: 256 threads x 8
 #ifndef ACGPU_EO_SPIN
-#define ACGPU_EO_SPIN (1u << 22)   // (lib/exp builds with 0 exercise the fallback of k_eo_scan)
+#define ACGPU_EO_SPIN (1u << 22)   // (a build with 0 exercises the fallback of k_eo_scan)
 #endif
 constexpr uint32_t kEoSpin = ACGPU_EO_SPIN;       // polls of a predecessor's word before a workgroup of the scan sums the buckets itself (~0.1 s)
 

@@ -48,13 +48,6 @@
 #include "launch_util.hpp"
 #include "pf_common.hpp"
 
-// PF_EXP: bit mask of timing experiments (scripts/pf_variants.sh); 0 in the product build.
-//   1 = no survivor handling   2 = no LDS gathers   4 = conflict-free gathers   8 = no level 1 at all
-//   32 = survivor loop with the second probe but no pushes / level 3   64 = survivor loop without the second probe
-#ifndef PF_EXP
-#define PF_EXP 0
-#endif
-
 namespace acgpu {
 
 namespace {
@@ -81,7 +74,6 @@ struct PfWave {
     uint32_t q2count = 0;    // wave-uniform fill level; a batch = the LAST (up to) 64 entries (order is irrelevant)
     uint32_t xcount = 0;     // wave-uniform: starts handed to level 3 so far (the probe's measure)
     uint4 ra[kSets] = {}, rb[kSets] = {};   // row-pair register sets (rows 2i / 2i+1 of the pair in set i % kSets)
-    uint32_t dummy = 0;      // PF_EXP experiments only
     bool carried = false;    // wave-uniform: sets 0..kSets-2 already receive the first pairs of the task to run
     int lane = 0;
     uint32_t amask = 0;
@@ -193,9 +185,7 @@ struct PfWave {
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const uint32_t h = pf_hash(key_at(wd, 2 * j + 1)) & amask;
-            if (PF_EXP & 2) word[j] = h;
-            else if (PF_EXP & 4) word[j] = s_bits[((h & 0xFF00u) | (uint32_t(lane) << 2)) >> 2];
-            else word[j] = s_bits[h >> 2];
+            word[j] = s_bits[h >> 2];
         }
     }
     template <int J>
@@ -244,7 +234,6 @@ struct PfWave {
             const uint32_t q = (i & 7u) * 2u + 1u;
             uint32_t next;
             const uint32_t win = window(wd, q, next);
-            if (PF_EXP & 64) { dummy += has ? win + next : 0u; continue; }   // experiment: peel + window only
             // the same probe as level 1 (key b[q+1..q+3], bits selected by b[q] and b[q+4]) in the second table
             bool ok_a, ok_b;
             if (X2) {   // the two exact candidate starts (q: key b[q..q+2], bit b[q+3]; q+1: key b[q+1..q+3], bit b[q+4])
@@ -257,7 +246,6 @@ struct PfWave {
                 const bool ok = has && int32_t((w2 << (win & 31)) | (w2 << (next & 31))) < 0;
                 ok_a = ok; ok_b = ok;   // either start may be the one: level 3 verifies both
             }
-            if (PF_EXP & 32) { dummy += uint32_t(ok_a) + uint32_t(ok_b); continue; }   // experiment: no pushes / level 3
             if (__any(ok_a | ok_b)) {
                 const uint64_t v = task_base + off + (second ? kRowBytes : 0u) + q;
                 push_q2(ok_a && v >= a.scan_lo && v < g.emit_hi, v);
@@ -316,8 +304,7 @@ struct PfWave {
             constexpr uint32_t fm = FOLD ? 0x20202020u : 0u;   // (levels 1 and 2 only: level 3 reads the haystack itself)
             const uint32_t w0[5] = {wa.x | fm, wa.y | fm, wa.z | fm, wa.w | fm, uint32_t(__builtin_amdgcn_update_dpp(0, int(wa.x), 0x130, 0xF, 0xF, false)) | fm};
             const uint32_t w1[5] = {wb.x | fm, wb.y | fm, wb.z | fm, wb.w | fm, uint32_t(__builtin_amdgcn_update_dpp(0, int(wb.x), 0x130, 0xF, 0xF, false)) | fm};
-            uint32_t hits = (PF_EXP & 8) ? uint32_t((w0[0] ^ w1[1] ^ w0[2] ^ w1[3] ^ w0[4] ^ w1[4]) == 0x12345678u) : level1_pair(w0, w1);
-            if (PF_EXP & 1) hits = (hits == 0xFFFFu && w0[0] == 0x12345678u) ? 1u : 0u;
+            uint32_t hits = level1_pair(w0, w1);
             if (lane == 63) hits = 0;  // lane 63's 16 bytes are lane 0 of the next row
             survivors(hits, w0, w1, off);  // (start positions outside [scan_lo, emit_hi) are dropped before level 3)
             p += 2 * kRowBytes;
@@ -400,7 +387,6 @@ __global__ __launch_bounds__(kPfBlock) void k_pf_count(PfArgs a, ScanGeom g, uin
         if (is_interior(task_base)) st.template run_task<false>(task_base, next_base, next_interior);
         else st.template run_task<true>(task_base, next_base, next_interior);
     }
-    if (PF_EXP && st.dummy == 0x12345u) counts[0] = st.dummy;
     // final partial batch of level 3
     while (st.q2count) st.drain_q2(st.q2count < 64 ? st.q2count : 64);
     if (a.events) st.flush_events(1);

@@ -33,7 +33,7 @@
 //       the whole 8-byte window (12.6 VALU per position; when every pattern has nine bytes only every other position is
 //       probed -- level1_key8x2: one hash and one gather for two starts, 8.25 VALU per position); 0.4 % of the positions of
 //       prose survive and 94 % of those are true prefixes, so level 3 is the verifiers' work.  Its cost is the dependent gathers of the DEEPEST walk of a batch (~1.4 us each: the clock
-//       profile of -DPFX_PROF), hence: a prefix node below which the trie is one chain to a leaf carries
+//       profile in docs/DESIGN_rounds1-4.md section 3), hence: a prefix node below which the trie is one chain to a leaf carries
 //       a chain-tail record (HotTables::pfx_tails; level 3 = one round of independent gathers + a masked compare,
 //       pfx_verify_tails), and hits are queued by kind -- tail compares in s_hitq, walks in s_slowq -- and verified in
 //       batches of their own, between the rounds.
@@ -56,38 +56,13 @@ namespace {
 
 using namespace pfdev;
 
-#ifndef PFX_EXP
-#define PFX_EXP 0   // timing experiments only (scripts/pfx_variants.sh): 1 = verifiers drop the survivors, 2 = drop the level-2 hits, 4 = hand-off without its stores (second pass sees no hits), 8 = the 8-byte level 1 loads its rows with plain (temporal) loads, 16 = the long key is read back, the map is not consulted
-#endif
-#ifndef PFX_PRODUCERS
-#define PFX_PRODUCERS 12
-#define PFX_VERIFIERS 4
-#endif
 // wave roles per workgroup (template parameters of the kernel): 12 streaming producers + 4 verifiers for the 4-byte level 2
 // (random text against 100 000 patterns: 3 % of the positions survive, 4 % of those hit); 8 + 8 for the long-prefix
 // level 2, whose verifiers do two dependent gathers per survivor on inputs where 7 % of the positions survive
 // (measured on English text: 12+4 1.77 ms, 10+5 1.63 ms, 8+8 1.28 ms per GiB)
-#ifndef PFX_LONG_PRODUCERS
-#define PFX_LONG_PRODUCERS 8
-#define PFX_LONG_VERIFIERS 8
-#endif
-// -DPFX_PROF=1 (timing experiments, lib/exp only): where the wavefronts of k_pfx_count spend their clocks.  g_pfx_prof:
-// [0] producer clocks, [1] of which waiting for ring room, [2] such waits; [3] verifier clocks, [4] idle (nothing to pop),
-// [5] levels 1-2 of its rounds, [6] level 3 (drain_hits), [7] rounds, [8] survivors popped, [9] level-3 batches, [10] hits verified,
-// [11] clocks in the event flushes, [12] trips of the walk loop (the lane with the most), [13] clocks / [14] batches / [15] hits
-// of the slow queue's walks
-#ifdef PFX_PROF
-__device__ unsigned long long g_pfx_prof[16];
-#define PFX_CLOCK() clock64()
-#define PFX_PROF_ADD(i, v) atomicAdd(&g_pfx_prof[i], static_cast<unsigned long long>(v))
-#else
-#define PFX_CLOCK() 0ull
-#define PFX_PROF_ADD(i, v) ((void)(v))
-#endif
-#ifndef PFX_RING
-#define PFX_RING 256
-#endif
-constexpr int kXQueue = PFX_RING;                             // ring entries per producer: {4-byte window, position}, 8 bytes; the position alone (4 bytes) under the 8-byte level 1
+constexpr int kPfxProducers = 12, kPfxVerifiers = 4;
+constexpr int kPfxLongProducers = 8, kPfxLongVerifiers = 8;
+constexpr int kXQueue = 256;                               // ring entries per producer: {4-byte window, position}, 8 bytes; the position alone (4 bytes) under the 8-byte level 1
 constexpr int kXBatch = 4;                                 // survivors per verifier lane per round
 
 // LDS words shared between wavefronts (ring indices, done flags).  Explicit address space: through a generic `volatile`
@@ -111,7 +86,6 @@ struct PfxProducer {
     uint32_t* task_seq_pub;        // LDS word where the current task sequence number is published
     uint32_t task_seq = 0;         // k: this producer's k-th task
     uint32_t tail_local = 0;       // wave-uniform copy of *tail
-    unsigned long long prof_stall = 0, prof_stalls = 0;   // (PFX_PROF)
     uint32_t head_cached = 0;      // wave-uniform: the last value of *head this wave has read (<= the real one)
     uint64_t task_base = 0;
     uint4 ra[kSets] = {}, rb[kSets] = {};
@@ -289,9 +263,7 @@ struct PfxProducer {
             // room for n entries?  (the verifier advances *head; spin while the ring is full)
             if (tail_local + n - head_cached > uint32_t(kQ)) {
                 if (dirty) { pf_fence(); if (lane == 0) lds_poke(tail, tail_local); dirty = false; }   // let the verifier see what is there
-                const unsigned long long w0 = PFX_CLOCK();
                 while (tail_local + n - (head_cached = lds_peek(head)) > uint32_t(kQ)) __builtin_amdgcn_s_sleep(2);
-                prof_stall += PFX_CLOCK() - w0; prof_stalls++;
             }
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
             if (KEY8) { if (ok) *(lds_u32*)(reinterpret_cast<uint32_t*>(ring) + ((tail_local + rank) & uint32_t(kQ - 1))) = uint32_t(entry >> 32); }
@@ -346,7 +318,6 @@ struct PfxProducer {
         typedef unsigned v4u __attribute__((ext_vector_type(4)));
         auto load_plain = [&](uint64_t p, uint4& w) {
             ACGPU_HAY_CHECK(g, p, 16);
-            if ((PFX_EXP & 8) && KEY8) { w = *reinterpret_cast<const uint4*>(g.hay16 + p); return; }
             const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(g.hay16 + p));
             w = make_uint4(t.x, t.y, t.z, t.w);
         };
@@ -591,8 +562,7 @@ __device__ __forceinline__ bool pfx_verify_tails(const PfArgs& a, const ScanGeom
 // trie row per byte), so a verifier wavefront's throughput is the number of walks it keeps in flight.
 template <int N, int kCap>
 __device__ __forceinline__ bool pfx_verify_n_from(const PfArgs& a, const ScanGeom& g, uint32_t* counts, const uint64_t (&v)[N],
-                                                  const uint32_t (&node)[N], PfxEv* ebuf, uint32_t* ecnt, const uint8_t* s_acls,
-                                                  unsigned long long* prof_steps = nullptr) {
+                                                  const uint32_t (&node)[N], PfxEv* ebuf, uint32_t* ecnt, const uint8_t* s_acls) {
     bool buffered = false;
     uint32_t s[N];
     uint64_t at[N];
@@ -636,9 +606,6 @@ __device__ __forceinline__ bool pfx_verify_n_from(const PfArgs& a, const ScanGeo
     }
 #pragma unroll 1
     for (uint32_t k = 0; any_live; k++) {
-#ifdef PFX_PROF
-        if (prof_steps && __builtin_amdgcn_ballot_w64(any_live) != 0) prof_steps[0]++;   // (trips of the wavefront)
-#endif
         uint32_t e[N];
 #pragma unroll
         for (int i = 0; i < N; i++) {
@@ -774,7 +741,7 @@ struct PfxHits {
 template <bool kLong, int kXProducers, int kXVerifiers, bool kGate = false, bool kKey8 = false, bool kX2 = false, bool kShort = false>
 __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, uint32_t* __restrict__ counts, PfxHits hl) {
     static_assert(kX2 || !kShort, "short mode: the every-other-position level 1 only");
-    static_assert(kXProducers + kXVerifiers <= kPfWaves && kXProducers % kXVerifiers == 0, "wave roles");
+    static_assert(kXProducers + kXVerifiers == kPfWaves && kXProducers % kXVerifiers == 0, "wave roles");
     static_assert(!(kLong && kGate), "the gate fronts the 4-byte map");
     static_assert(kLong || !kKey8, "the 8-byte level 1 goes with the long-prefix level 2");
     static_assert(kKey8 || !kX2, "every other position: the 8-byte level 1 only");
@@ -785,8 +752,8 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
     __shared__ __attribute__((aligned(16))) uint32_t s_bits[kPfxBitsBytes / 4];
     constexpr int kQ = kXQueue;   // entries per ring: 8 bytes each, 4 under the 8-byte level 1 (the position alone)
     __shared__ __attribute__((aligned(16))) uint64_t s_ring[kXProducers][kKey8 ? kQ / 2 : kQ];
-    // per-verifier event buffer: large where LDS has room (the 8-byte level 1 with 4 verifiers or fewer: its rings are half the size)
-    constexpr int kEvX = (kKey8 && kXVerifiers <= 2) ? 256 : kKey8 ? 128 : kEvBuf, kEvXFlush = kEvX == kEvBuf ? kEvFlush : kEvX - 64;
+    // per-verifier event buffer: large where LDS has room (the 8-byte level 1 with its 4 verifiers: its rings are half the size)
+    constexpr int kEvX = kKey8 ? 128 : kEvBuf, kEvXFlush = kEvX == kEvBuf ? kEvFlush : kEvX - 64;
     __shared__ PfxEv s_ev[kXVerifiers][kEvX];
     __shared__ uint8_t s_acls[256];
     // hits per level-3 batch: one per lane; two under the 8-byte level 1 (three and four were measured: nothing / slower)
@@ -807,11 +774,9 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t task_bytes = uint64_t(kTaskRows) * kRowBytes;
-    if (wave >= kXProducers + kXVerifiers) return;   // (role experiments with fewer than 16 active wavefronts)
     if (wave < kXProducers) {
         // ---------------------------------------------------------------- producer
         PfxProducer<kQ> st{a, g, s_bits, s_ring[wave], &s_tail[wave], &s_head[wave], &s_task[wave]};
-        [[maybe_unused]] const unsigned long long prof_t0 = PFX_CLOCK();
         st.lane = lane;
         const uint64_t prod_id = uint64_t(blockIdx.x) * kXProducers + wave;
         const uint64_t n_prod = uint64_t(gridDim.x) * kXProducers;
@@ -828,7 +793,6 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
         }
         pf_fence();
         if (lane == 0) lds_poke(&s_done[wave], 1u);   // (LDS executes a wavefront's operations in order: after its last tail)
-        if (lane == 0) { PFX_PROF_ADD(0, PFX_CLOCK() - prof_t0); PFX_PROF_ADD(1, st.prof_stall); PFX_PROF_ADD(2, st.prof_stalls); }
         return;
     }
     // -------------------------------------------------------------------- verifier
@@ -847,17 +811,13 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
     // (3 % hits): their few walks hide behind it, while a second pass pays for the same random HBM gathers on its own
     // (+1 ms on 5 ms).  (Requiring a nearly full ring as well changed nothing measurable.)
     uint32_t cand_acc = 0, hit_acc = 0;
-    [[maybe_unused]] unsigned long long prof_v0 = PFX_CLOCK(), prof_idle = 0, prof_l2 = 0, prof_l3 = 0, prof_rounds = 0, prof_surv = 0, prof_batches = 0, prof_hits = 0, prof_steps = 0, prof_flush = 0, prof_slow = 0, prof_slow_batches = 0, prof_slow_hits = 0;
     uint64_t* slowq = s_slowq[kKey8 ? vw : 0];
     uint32_t slow_n = 0;   // wave-uniform
     PfxEoPend<kEvX> eo_pend;
     auto flush_if = [&](bool buffered) {
-        const unsigned long long f0 = PFX_CLOCK();
         if (a.events && __builtin_amdgcn_ballot_w64(buffered) != 0) pfx_flush_events<kEvX>(a, lane, ebuf, ecnt, kEvXFlush, eo_pend);
-        prof_flush += PFX_CLOCK() - f0;
     };
     auto drain_hits = [&](uint32_t n) {   // level 3 for the LAST n queued hits (order is irrelevant)
-        const unsigned long long d0 = PFX_CLOCK(); prof_batches++; prof_hits += n;
         pf_fence();
         hit_n -= n;
         uint64_t e[kWalks];
@@ -867,7 +827,7 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
         if (hl.hits && hit_acc * 8 >= cand_acc && seg_fill + n <= hl.seg_cap) {   // second pass will walk them (k_pfx_verify)
 #pragma unroll
             for (int w = 0; w < kWalks; w++)
-                if (uint32_t(lane) + 64u * w < n && !(PFX_EXP & 4)) hl.hits[uint64_t(seg) * hl.seg_cap + seg_fill + 64 * w + lane] = e[w];
+                if (uint32_t(lane) + 64u * w < n) hl.hits[uint64_t(seg) * hl.seg_cap + seg_fill + 64 * w + lane] = e[w];
             seg_fill += n;
             return;
         }
@@ -884,7 +844,7 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
                 any_node |= node[w]; any_tail |= tail1[w];
             }
             if (any_tail) buffered |= pfx_verify_tails<kWalks, kEvX>(a, g, counts, v, tail1, ebuf, ecnt, s_acls);
-            if (any_node) buffered |= pfx_verify_n_from<kWalks, kEvX>(a, g, counts, v, node, ebuf, ecnt, s_acls, &prof_steps);
+            if (any_node) buffered |= pfx_verify_n_from<kWalks, kEvX>(a, g, counts, v, node, ebuf, ecnt, s_acls);
         } else if (uint32_t(lane) < n) {
             uint64_t v;
             uint32_t node, tail1;
@@ -894,10 +854,8 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
             else if (node) buffered = pfx_verify_from<false, kEvX>(a, g, counts, v, node, ebuf, ecnt, s_acls);
         }
         flush_if(buffered);
-        prof_l3 += PFX_CLOCK() - d0;
     };
     auto drain_slow = [&](uint32_t n) {   // the walks: the LAST n <= 64 entries of the slow queue, one per lane
-        const unsigned long long d0 = PFX_CLOCK(); prof_slow_batches++; prof_slow_hits += n;
         pf_fence();
         slow_n -= n;
         const uint64_t e = uint32_t(lane) < n ? slowq[slow_n + lane] : 0;
@@ -907,9 +865,8 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
         if (uint32_t(lane) < n) pfx_hit_decode(a, e, v[0], node[0], tail1);
         bool buffered = false;
         if (tail1) buffered = pfx_verify_tail<kEvX, true>(a, g, counts, v[0], tail1, ebuf, ecnt, s_acls);   // a node with several tail records
-        if (__any(node[0] != 0)) buffered |= pfx_verify_n_from<1, kEvX>(a, g, counts, v, node, ebuf, ecnt, s_acls, &prof_steps);
+        if (__any(node[0] != 0)) buffered |= pfx_verify_n_from<1, kEvX>(a, g, counts, v, node, ebuf, ecnt, s_acls);
         flush_if(buffered);
-        prof_slow += PFX_CLOCK() - d0;
     };
     // levels 2 and 3 for the survivors of one round: ent = ring entries (the 4-byte window in the low word), rel = v - row0
     const uint64_t n_prod = uint64_t(gridDim.x) * kXProducers;
@@ -920,7 +877,6 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
         return (prod_id + uint64_t(seq) * n_prod) * task_bytes + (pos & 0xFFFFu);
     };
     auto process = [&](const uint64_t (&ent)[kRB], bool (&go)[kRB], auto&& rel_fn) {   // rel_fn(b) = v - row0 of slot b
-        if (PFX_EXP & 1) return;
         [[maybe_unused]] bool short_buffered = false;
         uint64_t rel[kRB];   // (the 4-byte level 2 needs it for its hits only: computed on demand there)
         if constexpr (kLong) {
@@ -971,7 +927,6 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
                 }
                 khi[b] = w[1] & himask;
                 klo[b] = kKey8 ? w[0] : uint32_t(ent[b]);   // (8-byte level 1: the ring entry carries no window)
-                if (PFX_EXP & 16) go[b] = go[b] && w[0] == 0x12345678u && w[1] == 0x9ABCDEF0u;   // (timing: the key is read, nothing is looked up)
             }
 #pragma unroll
             for (int b = 0; b < kRB; b++) {
@@ -1050,7 +1005,7 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
         // the round four times longer
 #pragma unroll
         for (int b = 0; b < kRB; b++) {
-            const bool hit = node[b] != 0 && !(PFX_EXP & 2);
+            const bool hit = node[b] != 0;
             const unsigned long long m = __ballot(hit);
             if (m == 0) continue;
             const uint64_t relb = kLong ? rel[b] : rel_fn(b);   // v - row0 < 2^43
@@ -1066,7 +1021,7 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
             if (hl.hits && hit_acc * 8 >= cand_acc && seg_fill + nh <= hl.seg_cap) {
                 // handed to the second pass straight from the registers: the stores of a whole round retire together
                 // with its level-2 gathers (through the hit queue every 64 hits waited for their own store: +1 ms per GiB)
-                if (hit && !(PFX_EXP & 4)) hl.hits[uint64_t(seg) * hl.seg_cap + seg_fill + rank] = entry;
+                if (hit) hl.hits[uint64_t(seg) * hl.seg_cap + seg_fill + rank] = entry;
                 seg_fill += nh;
                 continue;
             }
@@ -1124,9 +1079,7 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
             const uint32_t seq_cur = lds_peek(&s_task[pw]);   // >= the sequence number of every entry read above
             if (lane == 0) lds_poke(&s_head[pw], head_k + avail);   // the producer may reuse the slots
             const uint64_t prod_id = uint64_t(blockIdx.x) * kXProducers + uint32_t(pw);
-            const unsigned long long r0 = PFX_CLOCK(), l3_before = prof_l3; prof_rounds++; prof_surv += avail;
             process(ent, go, [&](int b) { return rel_of(ent[b], prod_id, seq_cur); });
-            prof_l2 += (PFX_CLOCK() - r0) - (prof_l3 - l3_before);
         }
         if (!any_work && hit_n) drain_hits(hit_n < kDrain ? hit_n : kDrain);   // idle: verify what is queued
         if (!any_work && slow_n) drain_slow(slow_n < kSlowDrain ? slow_n : kSlowDrain);
@@ -1138,26 +1091,14 @@ __global__ __launch_bounds__(kPfBlock) void k_pfx_count(PfArgs a, ScanGeom g, ui
                 empty = empty && lds_peek(&s_tail[vw * kXPerVerifier + k]) == lds_peek(&s_head[vw * kXPerVerifier + k]);
             if (empty) break;
         }
-        if (!any_work) { const unsigned long long i0 = PFX_CLOCK(); __builtin_amdgcn_s_sleep(8); prof_idle += PFX_CLOCK() - i0; }
+        if (!any_work) __builtin_amdgcn_s_sleep(8);
     }
     while (hit_n) drain_hits(hit_n < kDrain ? hit_n : kDrain);
     while (slow_n) drain_slow(slow_n < kSlowDrain ? slow_n : kSlowDrain);
-    if (hl.hits && lane == 0) hl.seg_n[seg] = (PFX_EXP & 4) ? 0u : seg_fill;
+    if (hl.hits && lane == 0) hl.seg_n[seg] = seg_fill;
     if (a.events) {
         pfx_flush_events<kEvX>(a, lane, ebuf, ecnt, 1, eo_pend);
         if (a.eo_bb && eo_pend.n) pfx_flush_slots<kEvX>(a, lane, eo_pend);
-    }
-#ifdef PFX_PROF
-    {   // walk-loop trips of the wavefront = the longest-living lane's count, batch by batch; summed per lane here, so take the maximum
-        unsigned long long m = prof_steps;
-        for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(m, o, 64); m = t > m ? t : m; }
-        if (lane == 0) PFX_PROF_ADD(12, m);
-    }
-#endif
-    if (lane == 0) {
-        PFX_PROF_ADD(3, PFX_CLOCK() - prof_v0); PFX_PROF_ADD(4, prof_idle); PFX_PROF_ADD(5, prof_l2); PFX_PROF_ADD(6, prof_l3);
-        PFX_PROF_ADD(11, prof_flush); PFX_PROF_ADD(13, prof_slow); PFX_PROF_ADD(14, prof_slow_batches); PFX_PROF_ADD(15, prof_slow_hits);
-        PFX_PROF_ADD(7, prof_rounds); PFX_PROF_ADD(8, prof_surv); PFX_PROF_ADD(9, prof_batches); PFX_PROF_ADD(10, prof_hits);
     }
 }
 
@@ -1229,14 +1170,6 @@ __global__ __launch_bounds__(kVfBlock) void k_pfx_verify(PfArgs a, ScanGeom g, u
 
 }  // namespace
 
-#ifdef PFX_PROF
-extern "C" int acgpu_debug_pfx_prof(unsigned long long* out16, int reset) {   // lib/exp builds only
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_pfx_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[16] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_pfx_prof), z, sizeof z) != hipSuccess) return -1; }
-    return 0;
-}
-#endif
-
 bool pf_uses_large_set(const HotTables& h, const PfRoute& route) {
     const uint32_t min_patterns = h.var.pfx_min_patterns >= 0 ? uint32_t(h.var.pfx_min_patterns) : kPfxMinPatterns;   // (variant)
     return h.pfx_ready && (h.n_patterns >= min_patterns || route.force_pfx);
@@ -1285,21 +1218,21 @@ hipError_t launch_pfx_count(const HotTables& h, const ScanGeom& g, uint32_t* cou
     if (e != hipSuccess) return e;
     if (a.n_tasks == 0) return hipSuccess;
     uint64_t blocks = uint64_t(device_cus());
-    // the long-key level 1 (variant pfx_key8 = 0 switches it off); its wave roles: variant pfx_key8_roles = producers of
-    // 12 | 14 (the verifiers see 0.4 % of the positions of English text instead of 7 %, so nearly every wavefront can stream)
+    // the long-key level 1 (variant pfx_key8 = 0 switches it off); its wave roles are 12 + 4 (the verifiers see 0.4 % of the
+    // positions of English text instead of 7 %, so nearly every wavefront can stream).  Per GiB of prose, with the two hit
+    // queues: 10 + 5 0.645 ms, 12 + 4 0.575, 14 + 2 0.70; 15 + 1 loses as well (profiles/r04_key8_steps.jsonl); 8 + 8 was
+    // measured -- 0.91 ms -- and no longer fits LDS beside the two hit queues
     const bool key8 = long_key && h.pfx_bits8 != nullptr && h.pfx_depth >= 5 && (h.var.pfx_key8 != 0 || h.pfx_short_n > 0);
-    int roles = h.var.pfx_key8_roles;   // (per GiB of prose, with the two hit queues: 10 + 5 0.645 ms, 12 + 4 0.575, 14 + 2 0.70)
-    if (roles != 14) roles = 12;   // (8 + 8 was measured -- 0.91 ms -- and no longer fits LDS beside the two hit queues)
     // short mode (the long-key tables hold the long patterns only): the one kernel that compares the stragglers, whatever the variants say
     const bool short_mode = h.pfx_short_n > 0 && long_key && h.pfx_bits8x2 != nullptr;
-    if (short_mode) roles = 12;
     a.short_n = short_mode ? h.pfx_short_n : 0;
     for (uint32_t i = 0; i < kPfxShortMax; i++) {
         const uint32_t j = i < h.pfx_short_n ? i : 0;   // (an unused slot repeats the first straggler)
         a.short_lo[i] = h.pfx_short_lo[j]; a.short_hi[i] = h.pfx_short_hi[j]; a.short_len[i] = h.pfx_short_len[j]; a.short_node[i] = h.pfx_short_node[j];
     }
-    const int kXProducers = key8 ? roles : long_key ? PFX_LONG_PRODUCERS : PFX_PRODUCERS;
-    const int kXVerifiers = key8 ? 16 - roles : long_key ? PFX_LONG_VERIFIERS : PFX_VERIFIERS;
+    const bool long_roles = long_key && !key8;
+    const int kXProducers = long_roles ? kPfxLongProducers : kPfxProducers;
+    const int kXVerifiers = long_roles ? kPfxLongVerifiers : kPfxVerifiers;
     const uint64_t need = (a.n_tasks + kXProducers - 1) / kXProducers;
     if (blocks > need) blocks = need;
     PfxHits hl{nullptr, nullptr, 0};
@@ -1320,21 +1253,20 @@ hipError_t launch_pfx_count(const HotTables& h, const ScanGeom& g, uint32_t* cou
         if ((e = hipMemsetAsync(hl.seg_n, 0, size_t(n_seg) * 4, s)) != hipSuccess) return e;
     }
     // ... probed at every other position when every pattern has nine bytes (variant pfx_key8_x2 = 0 switches it off)
-    const bool x2 = key8 && h.pfx_bits8x2 != nullptr && roles == 12 && (h.var.pfx_key8_x2 != 0 || short_mode);
+    const bool x2 = key8 && h.pfx_bits8x2 != nullptr && (h.var.pfx_key8_x2 != 0 || short_mode);
+    const dim3 grid{uint32_t(blocks)}, block{kPfBlock};
     if (x2 && short_mode) {
         a.bits = h.pfx_bits8x2;
-        k_pfx_count<true, 12, 4, false, true, true, true><<<dim3(uint32_t(blocks)), dim3(kPfBlock), 0, s>>>(a, g, counts, hl);
+        k_pfx_count<true, kPfxProducers, kPfxVerifiers, false, true, true, true><<<grid, block, 0, s>>>(a, g, counts, hl);
     } else if (x2) {
         a.bits = h.pfx_bits8x2;
-        k_pfx_count<true, 12, 4, false, true, true><<<dim3(uint32_t(blocks)), dim3(kPfBlock), 0, s>>>(a, g, counts, hl);
+        k_pfx_count<true, kPfxProducers, kPfxVerifiers, false, true, true><<<grid, block, 0, s>>>(a, g, counts, hl);
     } else if (key8) {
         a.bits = h.pfx_bits8;
-        const dim3 grid{uint32_t(blocks)}, block{kPfBlock};
-        if (roles == 14) k_pfx_count<true, 14, 2, false, true><<<grid, block, 0, s>>>(a, g, counts, hl);
-        else k_pfx_count<true, 12, 4, false, true><<<grid, block, 0, s>>>(a, g, counts, hl);   // (14 + 2 and 15 + 1 were measured and lose: profiles/r04_key8_steps.jsonl)
-    } else if (long_key) k_pfx_count<true, PFX_LONG_PRODUCERS, PFX_LONG_VERIFIERS><<<dim3(uint32_t(blocks)), dim3(kPfBlock), 0, s>>>(a, g, counts, hl);
-    else if (use_gate) k_pfx_count<false, PFX_PRODUCERS, PFX_VERIFIERS, true><<<dim3(uint32_t(blocks)), dim3(kPfBlock), 0, s>>>(a, g, counts, hl);
-    else k_pfx_count<false, PFX_PRODUCERS, PFX_VERIFIERS><<<dim3(uint32_t(blocks)), dim3(kPfBlock), 0, s>>>(a, g, counts, hl);
+        k_pfx_count<true, kPfxProducers, kPfxVerifiers, false, true><<<grid, block, 0, s>>>(a, g, counts, hl);
+    } else if (long_key) k_pfx_count<true, kPfxLongProducers, kPfxLongVerifiers><<<grid, block, 0, s>>>(a, g, counts, hl);
+    else if (use_gate) k_pfx_count<false, kPfxProducers, kPfxVerifiers, true><<<grid, block, 0, s>>>(a, g, counts, hl);
+    else k_pfx_count<false, kPfxProducers, kPfxVerifiers><<<grid, block, 0, s>>>(a, g, counts, hl);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (hl.hits) {
         k_pfx_scan_segments<<<dim3(1), dim3(1024), 0, s>>>(hl.seg_n, n_seg, seg_off);

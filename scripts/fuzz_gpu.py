@@ -49,7 +49,7 @@ while (only is not None and only) or (only is None and time.time() < t_end):
         # per-seed knob (read per call by the library): host haystacks searched piece by piece behind the copy
         os.environ["ACGPU_HOST_PIECE_MIB"] = "1" if rng.random() < 0.5 else "256"
         # per-seed engine variants of the automaton (acgpu_set_variant): the large-set filter for every set it can serve;
-        # its long-key level 1 without chain tails (a fifth of the seeds), with 14 + 2 wave roles (a third), probing every
+        # its long-key level 1 without chain tails (a fifth of the seeds), probing every
         # position (a third) or not at all (a tenth), without the bit-table gate (a fifth); the LDS walk's table flavour and
         # class form at random (forms that do not fit an automaton leave it without that engine, never with another result);
         # leftmost find_iter from the per-start table whatever the density (half of the seeds), in small windows
@@ -64,8 +64,7 @@ while (only is not None and only) or (only is None and time.time() < t_end):
             variants["eo_fused"] = 0                          # (the order pass as separate launches)
         if rng.random() < 0.3:
             variants["pfx_short"] = 0                         # (one or two stragglers beside long patterns: the set as a whole instead of short mode)
-        if rng.random() < 0.33:
-            variants["pfx_key8_roles"] = 14
+        rng.random()   # (this draw once picked a wave-role variant that is gone; kept so that a seed still names the same automaton)
         if rng.random() < 0.33:
             variants["pfx_key8_x2"] = 0
         if rng.random() < 0.1:

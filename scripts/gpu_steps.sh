@@ -1,8 +1,8 @@
 #!/bin/bash
 # One gpurun call = a list of named steps (replaces the per-call one-off scripts of earlier rounds).
 # usage: scripts/gpu_steps.sh <tag> step [step ...]      output: gpurun_out/<tag>/
-# steps: tests | tests:<pytest args> | smoke | bench | bench_prof | hot_ab | hot_pmc[:alpha] | defs[:filter] | defs_all |
-#        c4_ab | nat_ab | fuzz[:n] | c4_pmc | nat_pmc | minlen | trace:<defs>[@variant=v] | latency[:max MiB] | evidence
+# steps: tests | tests:<pytest args> | smoke | bench | bench_prof | hot_ab | hot_pmc[:alpha] | defs[:filter] | defs_prof:<filter> |
+#        defs_all | c4_ab | fuzz[:n] | minlen | trace:<defs>[@variant=v] | latency[:max MiB] | evidence | sh:<command>
 set -u
 cd "$(dirname "$0")/.."
 TAG=$1; shift
@@ -35,11 +35,8 @@ for step in "$@"; do
       log "rocprof exit $?"
       find "$OUT/prof" -name "*kernel_stats.csv" -exec cp {} "$OUT/bench_kernel_stats.csv" \;
       rm -rf "$OUT/prof"; head -8 "$OUT/bench_kernel_stats.csv" | cut -c1-200 ;;
-    c4_ab)   # config 4: default engine and the named walk, 8 GiB (crc of the records printed: variants must agree)
-      for v in ${arg:-default}; do
-        lib=""; [ "$v" != default ] && lib="ACGPU_LIB=$ROOT/aho-corasick_amd/lib/exp/libacgpu_pfx_$v.so"
-        env $lib timeout 300 python scripts/run_c4.py 8 auto 5 2>> "$OUT/c4.err" | tail -1 | sed "s/^{/{\"variant\": \"$v\", /" | tee -a "$OUT/c4_ab.jsonl"
-      done
+    c4_ab)   # config 4: default engine and the named walk, 8 GiB (crc of the records printed: the two must agree)
+      timeout 300 python scripts/run_c4.py 8 auto 5 2>> "$OUT/c4.err" | tail -1 | sed "s/^{/{\"variant\": \"default\", /" | tee -a "$OUT/c4_ab.jsonl"
       timeout 300 python scripts/run_c4.py 8 walk 2 2>> "$OUT/c4.err" | tail -1 | sed "s/^{/{\"variant\": \"walk\", /" | tee -a "$OUT/c4_ab.jsonl" ;;
     minlen)
       timeout 900 python scripts/minlen_sweep.py ${arg:-1} > "$OUT/minlen_sweep.jsonl" 2> "$OUT/minlen.err"; log "minlen exit $?"; cut -c1-330 "$OUT/minlen_sweep.jsonl" | tee -a "$OUT/summary.txt" ;;

@@ -293,7 +293,7 @@ def test_large_set_filter_with_verifier_wavefronts(npat, gate):
     """pfx_scan.hip (4-byte-key blocked Bloom table, producer / verifier wavefronts) forced for every set size it can
     serve: sparse and dense inputs, sub-spans of every alignment, shards, the non-overlapping iterator on top, and a
     haystack made of pattern prefixes (rings full, producers waiting for their verifier).  gate = 1: with the
-    exact-prefix bit table in front of the hash map and the map lookup in the second pass (off by default)."""
+    exact-prefix bit table in front of the hash map and the map lookup in the second pass (the default)."""
     forms = {"pfx_min_patterns": 1, "pfx_gate": gate}   # engine variants of the automata under test
     pats = orc.gen_patterns(npat, seed=0xAC05)
     n = 6 << 20
@@ -333,18 +333,18 @@ def test_large_set_filter_with_verifier_wavefronts(npat, gate):
         assert_same(lf.find_iter(dev(h2), as_numpy=True), olf.find_iter(h2, as_numpy=True), f"pfx {npat} find_iter")
 
 
-@pytest.mark.parametrize("minlen,tails,roles,x2", [(5, 1, 12, 1), (6, 1, 12, 1), (7, 1, 12, 1), (8, 1, 12, 1), (9, 1, 12, 1), (11, 1, 12, 1),
-                                                   (8, 0, 12, 1), (11, 0, 12, 1), (8, 1, 14, 1), (11, 1, 14, 1), (9, 1, 12, 0), (11, 1, 12, 0)])
-def test_large_set_filter_long_prefix_level2(minlen, tails, roles, x2):
+@pytest.mark.parametrize("minlen,tails,x2", [(5, 1, 1), (6, 1, 1), (7, 1, 1), (8, 1, 1), (9, 1, 1), (11, 1, 1),
+                                             (8, 0, 1), (11, 0, 1), (9, 1, 0), (11, 1, 0)])
+def test_large_set_filter_long_prefix_level2(minlen, tails, x2):
     """pfx_scan.hip with the long-prefix map (HotTables::pfx_map8): when the shortest pattern has 5..8+ bytes, level 2
     compares min(8, shortest) bytes exactly (bytes 4.. fetched from the haystack by the verifier).  Patterns sharing
     4..7-byte prefixes, occurrences touching both ends of the span, spans ending inside a prefix, shards, a haystack
     made of pattern prefixes (hit-dense: level 3 goes to the second pass).  tails = 0: without the chain-tail records
     behind the map (level 3 walks the trie from the prefix node for every hit; with them only where the trie branches,
     a pattern ends inside the chain, or the span ends within 16 bytes)."""
-    # engine variants: producers of the 16 wavefronts under the long-key level 1 (12 = default); x2 = 0: from 9-byte patterns
-    # on that level 1 probes every other position (one hash for two starts) -- off here
-    forms = {"pfx_min_patterns": 1, "pfx_tails": tails, "pfx_key8_roles": roles, "pfx_key8_x2": x2}
+    # engine variants: x2 = 0: from 9-byte patterns on the long-key level 1 probes every other position (one hash for two
+    # starts) -- off here
+    forms = {"pfx_min_patterns": 1, "pfx_tails": tails, "pfx_key8_x2": x2}
     rng = np.random.default_rng(minlen)
     base = orc.gen_patterns(3000, seed=0xAC06 + minlen, lo=0x61, span=26)
     pats = []
