@@ -640,6 +640,29 @@ class AhoCorasick:
                             extra=(C.c_size_t(shard_begin), C.c_size_t(shard_end)))
         return self._wrap(arr, as_numpy)
 
+    def count_patterns(self, input, shard=None, out=None, accumulate=False, profile=None):
+        """Occurrences per pattern (acgpu_count_patterns): out[p] = how many matches of pattern p the overlapping search of
+        `input` reports (of its `shard`, if given), without producing the matches.  Returns a numpy uint64 array; with
+        out= a CUDA int64/uint64 tensor of patterns_len() elements the counts are left on the device (torch's current
+        stream) and `out` is returned -- accumulate=True adds to what it holds."""
+        inp = _as_input(input)
+        n = self.patterns_len()
+        if out is not None:
+            import torch
+            if not (_is_torch(out) and out.is_cuda and out.is_contiguous() and out.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))):
+                raise TypeError("out must be a contiguous CUDA int64/uint64 tensor")
+            ptr, n = out.data_ptr(), int(out.numel())
+        else:
+            host = np.empty(n, dtype=np.uint64)
+            ptr = host.ctypes.data
+        ci, ref = self._cinput(inp, out_on_device=out is not None)
+        sb, se = (inp.start(), inp.end()) if shard is None else shard
+        rc = self._L.acgpu_count_patterns(self._h, C.byref(ci), sb, se, C.c_void_p(ptr), n, 1 if accumulate else 0, None,
+                                          None if profile is None else C.byref(profile))
+        if rc:
+            _raise(rc)
+        return host if out is None else out
+
     def overlapping_device(self, hay_tensor, span=None, shard=None, out=None, profile=None, stream=None):
         """Device-to-device form: `hay_tensor` and `out` are torch CUDA tensors; returns the number of matches.
 

@@ -110,9 +110,10 @@ struct Scratch {
     DevBuf triev, triseg, trictr;                  // contiguous-NFA walk: match events of the count pass (cnfa_tri.hip)
     DevBuf lwev, lwtn, lwovf;                      // LDS walk: match events of the count walk by task, their counts, the overflow word (lds_emit.hip)
     uint32_t lw_gen = 0;                           // ... generation of the overflow word (a new value per call; the word is zeroed when made)
+    DevBuf hist, hcounts;                          // pattern counts (capi_count.cpp): visits[match states] + the total word; device copy of host-resident counts
     DevBuf probe;                                  // prefix-filter probe: 8 counters + the decision word at byte 64 (zeroed once)
     bool probe_ready = false;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[8] = {};   // [0..4] the overlapping search's legs, [6..7] around the record histogram of a pattern count
     bool ev_armed = false;        // evrank[] == 0 and evctr[] == 0 (the invariant k_ev_write restores; false after a failed call)
     bool events_served = false;   // the last internal-mode search on this scratch took its records from the prefix filter's events
     bool rank_over = false;       // ... which had more events than the all-pairs rank takes

@@ -486,6 +486,7 @@ EngineFacts engine_facts(const acgpu_automaton* aut, const DeviceState* ds) {
     f.has_dfa = ds->da.has_dfa; f.pf_ready = ds->hot.pf_ready; f.lw_ready = ds->hot.lw_ready; f.pfx_ready = ds->hot.pfx_ready;
     f.lw_full = ds->var.lw_first != 0 && lw_fill_supported(ds->hot);
     f.min_pattern_len = aut->nnfa.min_pattern_len; f.want = aut->cfg.engine; f.routing = ds->var.routing != 0;
+    f.count_hist = ds->var.count_hist != 0;
     return f;
 }
 static_assert(kPlanDfaWalk == ENG_DFA && kPlanCnfaWalk == ENG_CNFA && kPlanLdsWalk == ENG_HOT && kPlanPrefixFilter == ENG_PF &&

@@ -35,6 +35,12 @@ struct HotTables {
     uint32_t* lw_image = nullptr;   // LDS image: class map (512 B) | tables (host/lw_tables.hpp)
     uint32_t lw_image_bytes = 0;
     LwHostTables lw;                // flavour, class form and table offsets of the image (its host copy is dropped after the upload)
+    // ... and the match lists of its match states in hid order, for the state-visit count (lds_hist.hip): CSR over
+    // hid - first_match, pattern ids in the reference's order
+    uint32_t* hist_moff = nullptr;  // [hist_states + 1]
+    uint32_t* hist_mpid = nullptr;
+    uint32_t hist_states = 0;       // match states = bins of the state-visit walk
+    uint32_t hist_max_list = 0;     // longest match list
 
     // --- prefix-filter engine (pf_scan.hip) ---
     bool pf_ready = false;
@@ -98,6 +104,8 @@ struct HotTables {
         if (pfx_tails) (void)hipFree(pfx_tails);
         if (pfx_map) (void)hipFree(pfx_map);
         if (lw_image) (void)hipFree(lw_image);
+        if (hist_moff) (void)hipFree(hist_moff);
+        if (hist_mpid) (void)hipFree(hist_mpid);
         if (pf_bits3) (void)hipFree(pf_bits3);
         if (pf_bits) (void)hipFree(pf_bits);
         if (pf_bits2) (void)hipFree(pf_bits2);
@@ -302,6 +310,15 @@ hipError_t launch_lw_ev_emit(const HotTables& h, const ScanGeom& g, const void* 
                              uint32_t gen, const uint32_t* counts, const uint64_t* totals, uint64_t cap, acgpu_match* out, hipStream_t s,
                              // (enqueue-only form: report[0] <- records; report[1] <- 0, or UINT64_MAX on an overflow nobody fills)
                              uint64_t* report = nullptr, bool report_fail = false);
+// Per-pattern occurrence counts (lds_hist.hip).  State-visit form: launch_lw_hist walks g like launch_hot_count but counts
+// the VISITS of every match state (visits[h.hist_states], 64-bit, zero on entry); launch_hist_expand adds visits[s] to
+// counts[p] for every pattern p in the list of s, and the number of occurrences to *total.  Records form:
+// launch_hist_records counts the patterns of n ordered match records.  agree: the wave-agreement shortcut of hot bins.
+hipError_t launch_lw_hist(const HotTables& h, const ScanGeom& g, unsigned long long* visits, hipStream_t s, bool agree = true);
+hipError_t launch_hist_expand(const HotTables& h, const unsigned long long* visits, unsigned long long* counts, unsigned long long* total, hipStream_t s);
+hipError_t launch_hist_records(const acgpu_match* records, uint64_t n, unsigned long long* counts, uint64_t n_counts, hipStream_t s);
+// zeroes a[0..na) and b[0..nb) (64-bit words) with one launch
+hipError_t launch_hist_zero(unsigned long long* a, uint64_t na, unsigned long long* b, uint64_t nb, hipStream_t s);
 bool hot_fill_supported(const HotTables& h, const ScanGeom& g);
 hipError_t launch_hot_fill(const HotTables& h, const DevAutomaton& a, const ScanGeom& g, const uint64_t* active,
                            const uint64_t* totals, uint64_t cap, uint64_t max_waves, const uint64_t* aoff,

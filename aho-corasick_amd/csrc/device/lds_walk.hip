@@ -54,6 +54,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
+#include <vector>
 
 #include "../host/lw_tables.hpp"
 #include "hot.hpp"
@@ -323,6 +324,22 @@ hipError_t build_lw_tables(const NNfa& n, const Dfa& d, const std::vector<uint32
         const double rate = 3200.0 / (1.0 + 3.9 * p);
         out.lw_route_cb = uint32_t(std::max(124.0, 812500.0 / rate - 130.0));
     }
+    {
+        // the match lists in hid order for the state-visit count (lds_hist.hip), from the DFA's lists through order[h] - 2:
+        // the mapping the image's own lists use (host/lw_tables.cpp)
+        std::vector<uint32_t> moff(1, 0), mpid;
+        for (size_t hh = first_match; hh < order.size(); hh++) {
+            const uint32_t o = order[hh] - 2;
+            mpid.insert(mpid.end(), d.mpid.begin() + d.moff[o], d.mpid.begin() + d.moff[o + 1]);
+            moff.push_back(uint32_t(mpid.size()));
+            out.hist_max_list = std::max(out.hist_max_list, d.moff[o + 1] - d.moff[o]);
+        }
+        out.hist_states = uint32_t(moff.size() - 1);
+        if ((e = hipMalloc(reinterpret_cast<void**>(&out.hist_moff), moff.size() * 4)) != hipSuccess) return e;
+        if ((e = hipMemcpy(out.hist_moff, moff.data(), moff.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
+        if ((e = hipMalloc(reinterpret_cast<void**>(&out.hist_mpid), std::max<size_t>(mpid.size(), 1) * 4)) != hipSuccess) return e;
+        if (!mpid.empty() && (e = hipMemcpy(out.hist_mpid, mpid.data(), mpid.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
+    }
     t.image.clear();
     t.image.shrink_to_fit();
     out.lw = t;   // offsets, flavour, class form (the image itself lives on the device)
@@ -330,7 +347,6 @@ hipError_t build_lw_tables(const NNfa& n, const Dfa& d, const std::vector<uint32
     return hipSuccess;
 }
 
-namespace {
 LwArgs lw_args(const HotTables& h) {
     const LwHostTables& t = h.lw;
     LwArgs la{};
@@ -343,7 +359,6 @@ LwArgs lw_args(const HotTables& h) {
     la.list_col = t.classes;
     return la;
 }
-}  // namespace
 
 // The record fill of the one-row-per-state form: available when the match lists fit LDS beside the rows.
 bool lw_fill_supported(const HotTables& h) { return h.lw_ready && h.lw.flavour == kLwFull && h.lw.mlist_off != 0; }
@@ -365,10 +380,7 @@ hipError_t launch_lw_fill(const HotTables& h, const ScanGeom& g, const uint64_t*
     return hipGetLastError();
 }
 
-hipError_t launch_hot_count(const HotTables& h, const DevAutomaton& a, const ScanGeom& g, uint32_t* counts, hipStream_t s) {
-    if (!h.lw_ready) return hipErrorInvalidValue;
-    const LwHostTables& t = h.lw;
-    LwArgs la = lw_args(h);
+int lw_lane_geometry(const HotTables& h, const ScanGeom& g, LwArgs& la) {
     // lane-chunks: the count chunk split into a power-of-two number of pieces of >= kLwLaneChunk bytes (multiples of 64)
     // 512-byte lane-chunks by default; on the largest shards (from 6 GiB on) 1 024-byte ones halve the share of the
     // warm-up line (fabric reads 1.25x -> 1.13x the haystack, +2 % at 8 GiB: profiles/r03_hot_pmc.json, r03_hot_ab.jsonl).
@@ -384,12 +396,23 @@ hipError_t launch_hot_count(const HotTables& h, const DevAutomaton& a, const Sca
     la.warm_pieces = (g.halo + 15) / 16;
     la.n_lane_chunks = g.n_chunks * m;
     la.n_tasks = (la.n_lane_chunks + 63) / 64;
+    return up;
+}
+
+uint64_t lw_walk_blocks(const LwArgs& la) {
+    const uint64_t blocks = uint64_t(device_cus());
+    const uint64_t need = (la.n_tasks + kLwWaves - 1) / kLwWaves;
+    return blocks > need ? need : blocks;
+}
+
+hipError_t launch_hot_count(const HotTables& h, const DevAutomaton& a, const ScanGeom& g, uint32_t* counts, hipStream_t s) {
+    if (!h.lw_ready) return hipErrorInvalidValue;
+    const LwHostTables& t = h.lw;
+    LwArgs la = lw_args(h);
+    const int up = lw_lane_geometry(h, g, la);
     if (la.n_tasks == 0) return hipSuccess;
     if (h.lw_image_bytes > kLwLdsBytes) return hipErrorInvalidValue;
-    uint64_t blocks = uint64_t(device_cus());
-    const uint64_t need = (la.n_tasks + kLwWaves - 1) / kLwWaves;
-    if (blocks > need) blocks = need;
-    const dim3 grid{uint32_t(blocks)};
+    const dim3 grid{uint32_t(lw_walk_blocks(la))};
     if (up == 4) lw_launch<4>(t.flavour, t.computed_cls, grid, s, la, g, counts);
     else lw_launch<8>(t.flavour, t.computed_cls, grid, s, la, g, counts);
     return hipGetLastError();

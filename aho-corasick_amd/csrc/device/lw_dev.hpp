@@ -178,9 +178,11 @@ __device__ __forceinline__ uint32_t lw_redo4(const LwArgs& a, const LwLds& L, ui
 // Generic (edge) walk of one lane-chunk -- the first and last wave regions of a shard, and every chunk of a small
 // input: exact step, ownership from `lo`.  The bytes come in aligned 16-byte pieces (only pieces holding a live byte are
 // touched), two pieces ahead: a dependent global load per byte cost ~0.5 us each, 0.25 ms for one 512-byte chunk.
-template <int FLAV, bool CC>
-__device__ __forceinline__ uint32_t lw_edge_walk(const LwArgs& a, const LwLds& L, const ScanGeom& g, uint64_t w, uint64_t lo,
-                                                 uint64_t hi, uint32_t cnt) {
+// on_owned(h): the state behind handle h was entered by an owned byte (the count walk adds its match-list length, the
+// state-visit walk of lds_hist.hip bumps its bin).
+template <int FLAV, bool CC, class F>
+__device__ __forceinline__ void lw_edge_walk_each(const LwArgs& a, const LwLds& L, const ScanGeom& g, uint64_t w, uint64_t lo,
+                                                  uint64_t hi, F&& on_owned) {
     const uint8_t* hay16 = g.hay16;
     uint32_t h = a.start;
     const uint64_t p0 = w & ~uint64_t(15);
@@ -199,10 +201,15 @@ __device__ __forceinline__ uint32_t lw_edge_walk(const LwArgs& a, const LwLds& L
             const uint64_t v = p + k;
             if (v >= w && v < hi) {
                 h = lw_careful_step<FLAV, CC>(a, L, h, (wd[k >> 2] >> (8 * (k & 3))) & 0xFFu);
-                if (v >= lo) cnt += lw_match_len<FLAV>(a, L, h);
+                if (v >= lo) on_owned(h);
             }
         }
     }
+}
+template <int FLAV, bool CC>
+__device__ __forceinline__ uint32_t lw_edge_walk(const LwArgs& a, const LwLds& L, const ScanGeom& g, uint64_t w, uint64_t lo,
+                                                 uint64_t hi, uint32_t cnt) {
+    lw_edge_walk_each<FLAV, CC>(a, L, g, w, lo, hi, [&](uint32_t h) { cnt += lw_match_len<FLAV>(a, L, h); });
     return cnt;
 }
 
@@ -251,4 +258,13 @@ __device__ __forceinline__ void lw_step4(const LwArgs& a, const LwLds& L, const 
 }
 
 }  // namespace lwdev
+
+// ---- host side, shared by the launches of lds_walk.hip and lds_hist.hip
+// kernel arguments of the image of `h` (no geometry yet)
+lwdev::LwArgs lw_args(const HotTables& h);
+// lane-chunk geometry of a walk over g (the count chunk split into a power-of-two number of lane-chunks, whole 64- or
+// 128-byte units): fills la's geometry fields and returns the unit size in 16-byte pieces (8 | 4); la.n_tasks == 0: nothing to walk
+int lw_lane_geometry(const HotTables& h, const ScanGeom& g, lwdev::LwArgs& la);
+// persistent workgroups of 16 wavefronts for la.n_tasks wave tasks: one per CU, or fewer when the tasks are few
+uint64_t lw_walk_blocks(const lwdev::LwArgs& la);
 }  // namespace acgpu

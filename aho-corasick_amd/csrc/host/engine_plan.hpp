@@ -21,6 +21,7 @@ struct EngineFacts {
     size_t min_pattern_len = 0;
     int want = 0;                // acgpu_config.engine as the pipelines test it: 0 auto, 1 transition walk, 2 LDS walk, 3 prefix filter
     bool routing = true;         // variant `routing`
+    bool count_hist = true;      // variant `count_hist` (pattern counts only)
 };
 
 struct EnginePlan {
@@ -47,6 +48,18 @@ inline EnginePlan plan_engines(const EngineFacts& f) {
         else if (f.has_dfa) p.alternative = kPlanDfaWalk;
     }
     return p;
+}
+
+// How acgpu_count_patterns gets its per-pattern counts (capi_count.cpp): from the visits of the match states, counted by the
+// LDS walk and expanded through the match lists once per call (device/lds_hist.hip), or from the records of the
+// overlapping search, whatever engine produces them.  The state-visit form needs the LDS image, no empty pattern (every
+// state would be a match state: the LDS walk is not offered automatically there either), and an engine request it can
+// honour; variant count_hist = 0 forces the records form.  A split set is asked with lw_ready = false (it has no image of
+// its own).  Measured: profiles/count_hist_ab.txt.
+enum class CountForm : uint32_t { Records = 0, StateVisits = 1 };
+inline CountForm plan_count(const EngineFacts& f) {
+    const bool engine_ok = f.want == 0 || f.want == 2;   // AUTO or LDS_WALK
+    return f.lw_ready && f.min_pattern_len > 0 && engine_ok && f.count_hist ? CountForm::StateVisits : CountForm::Records;
 }
 
 // What the hints of the automaton make of a prefix-filter scan that has an alternative (spans of kProbeMinSpan and more,

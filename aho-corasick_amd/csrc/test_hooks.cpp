@@ -196,6 +196,16 @@ acgpu_status acgpu_test_engine_plan(const uint64_t* facts, const int32_t* hints,
     return ACGPU_OK;
 }
 
+// Test hook (NOT a search path): plan_count of host/engine_plan.hpp on explicit facts, or on those of an uploaded automaton.
+acgpu_status acgpu_test_count_plan(acgpu_automaton* aut, const uint64_t* facts, uint32_t* out) {
+    if (!out || (!aut && !facts)) return ACGPU_ERR_INVALID_ARGUMENT;
+    if (aut) return acgpu_count_plan_of(aut, out);
+    EngineFacts f;
+    f.lw_ready = facts[0] != 0; f.min_pattern_len = size_t(facts[1]); f.want = int(facts[2]); f.count_hist = facts[3] != 0;
+    out[0] = uint32_t(plan_count(f));
+    return ACGPU_OK;
+}
+
 // Test hook (NOT a search path): the sizing rules of host/ov_sizes.hpp, which both forms of the overlapping search apply, on explicit integers.
 acgpu_status acgpu_test_ov_sizes(int32_t rule, uint64_t a, uint64_t b, uint64_t c, uint64_t* out) {
     if (!out) return ACGPU_ERR_INVALID_ARGUMENT;

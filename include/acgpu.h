@@ -154,6 +154,7 @@ typedef struct acgpu_automaton acgpu_automaton;
  * plus ACGPU_GUARD_SHRINK in the bounds-checked debug flavour).  Names (aho-corasick_amd/csrc/host/variants.hpp):
  *   lw_flavour -1|0|1|2, lw_cls -1|0|1, lw_lane_chunk bytes            LDS walk: table flavour, class form, lane-chunk size
  *   lw_first 0|1, lw_events 0|1                                        small automata: the LDS walk before the prefix filter; records from its events
+ *   count_hist 0|1|2                                                   acgpu_count_patterns: from the records | from state visits where the LDS walk serves (plan_count, host/engine_plan.hpp) | ... without the hot-bin shortcut
  *   pfx_min_patterns n, pfx_gate 0|1, pfx_tails 0|1|2, pfx_key8 0|1, pfx_key8_x2 0|1, pfx_short 0|1   large-set filter (tails: none | chains | small subtrees; short: one or two stragglers of 3..8 bytes in the long set's pass)
  *   walk_literal 0|1, walk_tri 0|1, tri_events 0|1                     transition walks
  *   pf_classic 0|1, routing 0|1, eo_fused 0|1                          prefix filter result form / hand-over of abandoned scans / the order pass's histogram inside the scan
@@ -207,6 +208,25 @@ acgpu_status acgpu_find_overlapping_shard(acgpu_automaton* aut, const acgpu_inpu
                                           size_t shard_begin, size_t shard_end,
                                           acgpu_match* out, size_t cap, size_t* n_out,
                                           acgpu_profile* prof);
+
+/* Per-pattern occurrence counts (no reference counterpart; what `for m in find_overlapping_iter: counts[m.pattern] += 1`
+ * computes): counts[p] = the number of records with pattern p that acgpu_find_overlapping_shard returns for the same input
+ * and shard (same ownership rule: ends in (shard_begin, shard_end], plus the start-state matches when shard_begin ==
+ * span_start); *total (optional) = their sum for this call.  No record is written, ordered or copied where the LDS walk
+ * serves the automaton: it counts the visits of its match states and the match lists are expanded once per call
+ * (DESIGN.md 3.2c); every other automaton is counted from the record stream of the overlapping search, left in scratch.
+ * Argument checks and status codes are those of the overlapping search, in its order (a leftmost automaton:
+ * ACGPU_ERR_UNSUPPORTED_OVERLAPPING), then n_counts != acgpu_patterns_len(aut): ACGPU_ERR_INVALID_ARGUMENT (the reason in
+ * acgpu_last_error()) -- all before any device work.  `counts` is host memory, or device memory when input->out_on_device.
+ * The call zeroes it unless `flags` holds ACGPU_COUNT_ACCUMULATE (device-resident counts only, else
+ * ACGPU_ERR_INVALID_ARGUMENT): consecutive calls on one stream then add up -- a corpus walked shard by shard or file by
+ * file.  Synchronous.  prof: ms_scan the walk (or the overlapping search), ms_fill the expansion (or the record histogram),
+ * n_matches the total. */
+#define ACGPU_COUNT_ACCUMULATE 1u
+acgpu_status acgpu_count_patterns(acgpu_automaton* aut, const acgpu_input* input,
+                                  size_t shard_begin, size_t shard_end,
+                                  uint64_t* counts, size_t n_counts, uint32_t flags,
+                                  uint64_t* total, acgpu_profile* prof);
 
 /* Enqueue-only form of acgpu_find_overlapping_shard for pipelined callers (no reference counterpart): haystack,
  * `out` and `totals` are device memory; the call returns as soon as the kernels are enqueued on input->stream, so a

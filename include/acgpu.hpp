@@ -319,6 +319,18 @@ public:
     size_t patterns_len() const { return acgpu_patterns_len(h_.get()); }
     size_t memory_usage() const { return acgpu_memory_usage(h_.get()); }
     acgpu_automaton* raw() const { return h_.get(); }
+    // occurrences per pattern (acgpu_count_patterns) of the overlapping search over `input`: host counts, one per pattern
+    std::vector<uint64_t> count_patterns(const Input& input, uint64_t* total = nullptr) const {
+        acgpu_input in = input.raw();
+        std::vector<uint64_t> counts(patterns_len(), 0);
+        detail::check(acgpu_count_patterns(h_.get(), &in, in.span_start, in.span_end, counts.data(), counts.size(), 0, total, nullptr));
+        return counts;
+    }
+    // ... into device memory (input.raw().out_on_device), optionally on top of what an earlier call left there
+    void count_patterns_device(const acgpu_input& in, size_t shard_begin, size_t shard_end, uint64_t* dev_counts, bool accumulate = false,
+                               uint64_t* total = nullptr, acgpu_profile* prof = nullptr) const {
+        detail::check(acgpu_count_patterns(h_.get(), &in, shard_begin, shard_end, dev_counts, patterns_len(), accumulate ? ACGPU_COUNT_ACCUMULATE : 0u, total, prof));
+    }
     // an engine variant of this automaton (acgpu_set_variant; tests and A/B runs): before its first search
     void set_variant(const char* name, int32_t value) { detail::check(acgpu_set_variant(h_.get(), name, value)); }
 

@@ -48,6 +48,12 @@ acgpu_status acgpu_test_lw_event_records_host(const acgpu_automaton* aut, const 
 acgpu_status acgpu_test_engine_plan(const uint64_t* facts, const int32_t* hints, uint64_t span_bytes, int32_t first_kernel_is_large_set,
                                     uint32_t* out);
 
+/* Test hook, not a search path: which form acgpu_count_patterns takes (plan_count, aho-corasick_amd/csrc/host/engine_plan.hpp):
+ * out[0] = 1 state visits on the LDS walk | 0 records of the overlapping search.  aut == NULL: from explicit
+ * facts[0..3] = {LDS-walk tables, shortest pattern, requested engine (0 auto, 1 transition walk, 2 LDS walk, 3 prefix filter),
+ * variant count_hist}; else from the automaton as uploaded to the current device (facts ignored; needs a GPU). */
+acgpu_status acgpu_test_count_plan(acgpu_automaton* aut, const uint64_t* facts, uint32_t* out);
+
 /* Test hook, not a search path: the sizing rules of the overlapping search (aho-corasick_amd/csrc/host/ov_sizes.hpp) on
  * explicit integers; out: three words.
  *   rule 0: event-list capacity of a span of `a` bytes -> out[0].
