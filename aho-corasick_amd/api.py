@@ -20,6 +20,7 @@ from . import _lib
 
 # numpy view of acgpu_match / Match{pattern, span} (src/util/search.rs:825-830)
 MATCH_DTYPE = np.dtype([("pattern", "<u4"), ("_pad", "<u4"), ("start", "<u8"), ("end", "<u8")])
+NO_MATCH = 0xFFFFFFFF   # ACGPU_NO_MATCH: the pattern of a find_batch record whose segment has no match
 
 
 class MatchKind(enum.IntEnum):  # src/util/search.rs:1052-1074
@@ -659,6 +660,48 @@ class AhoCorasick:
         sb, se = (inp.start(), inp.end()) if shard is None else shard
         rc = self._L.acgpu_count_patterns(self._h, C.byref(ci), sb, se, C.c_void_p(ptr), n, 1 if accumulate else 0, None,
                                           None if profile is None else C.byref(profile))
+        if rc:
+            _raise(rc)
+        return host if out is None else out
+
+    BATCH_TILE_BYTES = 8192   # kBatchTile (csrc/host/engine_plan.hpp): the walk's staging tile per wavefront
+
+    def find_batch(self, haystack, offsets, anchored=False, earliest=False, out=None, profile=None):
+        """First match of every segment of a packed haystack (acgpu_find_batch): segment s is haystack[offsets[s]:offsets[s+1]]
+        and record s is what try_find returns for that span -- positions are offsets into `haystack`, no match is pattern ==
+        NO_MATCH with start = end = 0.  Host inputs (bytes / numpy uint8 with a numpy uint64 or int64 offsets array) return a
+        numpy MATCH_DTYPE array of len(offsets) - 1 records; a CUDA uint8 tensor with a CUDA int64 offsets tensor is searched
+        zero-copy on torch's current stream.  With out= a CUDA uint8 tensor of at least 24 bytes per segment the records stay on
+        the device and `out` is returned."""
+        ref = _HayRef(haystack)
+        if ref.on_device:
+            import torch
+            if not (_is_torch(offsets) and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64):
+                raise TypeError("a device haystack needs a contiguous CUDA int64 offsets tensor")
+            keep_off, optr, n_off = offsets, offsets.data_ptr(), int(offsets.numel())
+        else:
+            keep_off = np.ascontiguousarray(offsets)
+            if keep_off.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)) or keep_off.ndim != 1:
+                raise TypeError("a host haystack needs a one-dimensional numpy uint64 or int64 offsets array")
+            if keep_off.dtype == np.int64 and keep_off.size and int(keep_off.min()) < 0:
+                raise ValueError("negative offset")
+            optr, n_off = keep_off.ctypes.data, int(keep_off.size)
+        n = max(n_off - 1, 0)
+        stream = _device_call_stream(ref, None)
+        if out is not None:
+            import torch
+            if not (_is_torch(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and
+                    out.numel() >= n * MATCH_DTYPE.itemsize):
+                raise TypeError(f"out must be a contiguous CUDA uint8 tensor of at least {n * MATCH_DTYPE.itemsize} bytes")
+            if stream is None:
+                stream = torch.cuda.current_stream().cuda_stream or None
+            ptr = out.data_ptr()
+        else:
+            host = np.empty(n, dtype=MATCH_DTYPE)
+            ptr = host.ctypes.data
+        ci = _lib.CInput(ref.ptr, ref.n, 0, ref.n, int(bool(anchored)), int(bool(earliest)), ref.on_device, int(out is not None), stream)
+        rc = self._L.acgpu_find_batch(self._h, C.byref(ci), C.c_void_p(optr), n, C.c_void_p(ptr),
+                                      None if profile is None else C.byref(profile))
         if rc:
             _raise(rc)
         return host if out is None else out

@@ -439,6 +439,9 @@ acgpu_status acgpu_upload(acgpu_automaton* aut, int device) {
             ds->da.dfa.stride2 = uint32_t(d.stride2);
             ds->da.dfa.sp = {d.special.max_special_id, d.special.max_match_id, d.special.start_unanchored_id,
                              d.special.start_anchored_id};
+            // batched find: this DFA (the automaton's own semantics, whatever its match and start kind) as u16 rows for LDS
+            if (hipError_t e = upload_batch_tables(d, aut->nnfa.pattern_lens, aut->var.batch_rows != 0, ds->batch); e != hipSuccess)
+                return hip_fail(e, "upload_batch_tables");
             // LDS-resident fast path: Standard semantics, unanchored start
             // (StartKind::Both interleaves anchored copies, dfa.rs:617-724: generic walk only)
             if (unanchored_standard && aut->cfg.engine != 1) {

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "acgpu.h"
 #include "capi_internal.hpp"
+#include "device/batch_find.hpp"
 #include "device/cnfa_walk.hpp"
 #include "device/cnfa_tri.hpp"
 #include "device/cnfa_tri_step.hpp"
@@ -28,6 +29,7 @@
 #include "device/select.hpp"
 #include "device/start_select.hpp"
 #include "host/automaton.hpp"
+#include "host/batch_tables.hpp"
 #include "host/cnfa_tables.hpp"
 #include "host/cnfa_tri_tables.hpp"
 #include "host/devbuf.hpp"
@@ -111,6 +113,8 @@ struct Scratch {
     DevBuf lwev, lwtn, lwovf;                      // LDS walk: match events of the count walk by task, their counts, the overflow word (lds_emit.hip)
     uint32_t lw_gen = 0;                           // ... generation of the overflow word (a new value per call; the word is zeroed when made)
     DevBuf hist, hcounts;                          // pattern counts (capi_count.cpp): visits[match states] + the total word; device copy of host-resident counts
+    DevBuf boff, bout, blongs, bctl;               // batched find (capi_batch.cpp): device copies of host offsets / records, the list of long segments, the control words
+    uint64_t* bpin = nullptr;                      // ... and the page-locked landing zone of the control words and the head of that list
     DevBuf probe;                                  // prefix-filter probe: 8 counters + the decision word at byte 64 (zeroed once)
     bool probe_ready = false;
     hipEvent_t ev[8] = {};   // [0..4] the overlapping search's legs, [6..7] around the record histogram of a pattern count
@@ -129,6 +133,7 @@ struct Scratch {
     ~Scratch() {
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
         if (pinned) (void)hipHostFree(pinned);
+        if (bpin) (void)hipHostFree(bpin);
     }
 };
 
@@ -179,6 +184,7 @@ struct DeviceState {
     CnfaHotTables cnfa_hot;   // contiguous-NFA walk with the start state's neighbourhood in LDS (cnfa_walk.hip)
     CnfaTriTables cnfa_tri;   // contiguous-NFA walk that skips the depth <= 2 regime by a trigram bitmap in LDS (cnfa_tri.hip)
     DfaTriTables dfa_tri;     // the same skip in front of the DFA transition walk (dfa_tri.hip)
+    BatchTables batch;        // batched find: the DFA as u16 rows for LDS (batch_find.hip), and the facts of plan_batch
     bool derived_dfa = false;  // da.dfa was derived from an NFA-kind automaton at upload (device only)
     // > 0 while recent scans of this automaton were abandoned by the two-type filter (PfArgs::route_*): the next scans
     // ask the probe (launch_pf_probe, ~10 us) which engine to run instead of paying for an abandoned pass each; every
@@ -373,6 +379,8 @@ EngineFacts engine_facts(const acgpu_automaton* aut, const DeviceState* ds);
 acgpu_status enqueue_impl(acgpu_automaton* aut, const acgpu_input* in, size_t shard_begin, size_t shard_end, acgpu_match* out,
                           size_t cap, uint64_t* totals, int32_t slot, uint32_t flags, bool* probed, EnqueueGuess* guess = nullptr,
                           EnqueueSync* sync = nullptr);
+// ---- capi_batch.cpp
+BatchFacts batch_facts(const DeviceState* ds);
 // ---- capi_find.cpp
 acgpu_status serial_impl(acgpu_automaton* aut, const acgpu_input* in, bool single, acgpu_match* out, size_t cap,
                          size_t* n_out, acgpu_profile* prof);

@@ -36,6 +36,9 @@ struct acgpu_automaton {
 // the form acgpu_count_patterns takes for this automaton on the current device (host/engine_plan.hpp: plan_count; uploads the
 // automaton): *form = 1 state visits | 0 records
 acgpu_status acgpu_count_plan_of(acgpu_automaton* aut, uint32_t* form);
+// the stepper acgpu_find_batch walks this automaton with on the current device (host/engine_plan.hpp: plan_batch; uploads the
+// automaton): *form = 1 global DFA | 2 global contiguous NFA | 3 LDS rows
+acgpu_status acgpu_batch_plan_of(acgpu_automaton* aut, uint32_t* form);
 // bytes per lane-chunk of a search of this automaton (capi.cpp::default_chunk)
 uint32_t acgpu_default_chunk(const acgpu_automaton* aut, size_t span_len);
 // sets what acgpu_last_error() returns on this thread (multi.cpp mirrors its errors into it)

@@ -62,6 +62,29 @@ inline CountForm plan_count(const EngineFacts& f) {
     return f.lw_ready && f.min_pattern_len > 0 && engine_ok && f.count_hist ? CountForm::StateVisits : CountForm::Records;
 }
 
+// Which stepper the batched find walks with (acgpu_find_batch, capi_batch.cpp / device/batch_find.hip).  The workgroup has
+// kBatchWaves wavefronts with a staging tile of kBatchTile bytes each and a 256-byte class map; what is left of the 160 KiB
+// of LDS holds the automaton's own DFA as u16 rows of alphabet_len entries, every entry the PREMULTIPLIED row offset of the
+// next state -- so the image is limited by its entry count (65 408 entries; the offsets then fit 16 bits as well).  Automata
+// beyond that, and variant batch_rows = 0, walk the global tables: the DFA the device holds, else the contiguous NFA.
+constexpr uint32_t kBatchTile = 8192, kBatchWaves = 4, kBatchLdsBytes = 160 * 1024;
+constexpr uint32_t kBatchRowsMaxEntries = (kBatchLdsBytes - kBatchWaves * kBatchTile - 256) / 2;
+constexpr uint32_t kBatchLaneMaxDefault = 4 * kBatchTile;   // variant batch_lane_max = 0
+struct BatchFacts {
+    bool has_dfa = false;        // the device holds a DFA of the automaton itself (its own, or derived at upload)
+    uint64_t dfa_states = 0;     // ... with this many states (dead and fail included)
+    uint32_t alphabet_len = 0;   // ... and this many byte classes
+    bool batch_rows = true;      // variant `batch_rows`
+};
+enum class BatchForm : uint32_t { DfaWalk = 1, CnfaWalk = 2, LdsRows = 3 };   // (numbered as acgpu_engine)
+inline bool batch_rows_fit(uint64_t dfa_states, uint32_t alphabet_len) {
+    return dfa_states > 0 && alphabet_len > 0 && dfa_states * alphabet_len <= kBatchRowsMaxEntries;
+}
+inline BatchForm plan_batch(const BatchFacts& f) {
+    if (f.has_dfa && f.batch_rows && batch_rows_fit(f.dfa_states, f.alphabet_len)) return BatchForm::LdsRows;
+    return f.has_dfa ? BatchForm::DfaWalk : BatchForm::CnfaWalk;
+}
+
 // What the hints of the automaton make of a prefix-filter scan that has an alternative (spans of kProbeMinSpan and more,
 // and only while the first kernel is the two-type filter): take the alternative unasked, ask the probe first, or just scan.
 enum class PfStart : uint32_t { Scan = 0, Probe = 1, TakeAlternative = 2 };

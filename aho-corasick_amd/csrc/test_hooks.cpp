@@ -206,6 +206,17 @@ acgpu_status acgpu_test_count_plan(acgpu_automaton* aut, const uint64_t* facts, 
     return ACGPU_OK;
 }
 
+// Test hook (NOT a search path): plan_batch of host/engine_plan.hpp on explicit facts, or on those of an uploaded automaton.
+acgpu_status acgpu_test_batch_plan(acgpu_automaton* aut, const uint64_t* facts, uint32_t* out) {
+    if (!out || (!aut && !facts)) return ACGPU_ERR_INVALID_ARGUMENT;
+    out[1] = kBatchTile; out[2] = kBatchLaneMaxDefault; out[3] = kBatchRowsMaxEntries;
+    if (aut) return acgpu_batch_plan_of(aut, out);
+    BatchFacts f;
+    f.has_dfa = facts[0] != 0; f.dfa_states = facts[1]; f.alphabet_len = uint32_t(facts[2]); f.batch_rows = facts[3] != 0;
+    out[0] = uint32_t(plan_batch(f));
+    return ACGPU_OK;
+}
+
 // Test hook (NOT a search path): the sizing rules of host/ov_sizes.hpp, which both forms of the overlapping search apply, on explicit integers.
 acgpu_status acgpu_test_ov_sizes(int32_t rule, uint64_t a, uint64_t b, uint64_t c, uint64_t* out) {
     if (!out) return ACGPU_ERR_INVALID_ARGUMENT;

@@ -159,6 +159,7 @@ typedef struct acgpu_automaton acgpu_automaton;
  *   walk_literal 0|1, walk_tri 0|1, tri_events 0|1                     transition walks
  *   pf_classic 0|1, routing 0|1, eo_fused 0|1                          prefix filter result form / hand-over of abandoned scans / the order pass's histogram inside the scan
  *   start_table 0|1, ss_window_kib n, find_iter_windows 0|1, find_iter_start_table 0|1, find_iter_disjoint 0|1, stream_split 0|1   non-overlapping forms
+ *   batch_rows 0|1, batch_lane_max bytes, batch_blocks n                acgpu_find_batch: never the LDS image | longest segment a lane walks (0: 32 KiB) | workgroups of the walk (0: what the device holds)
  * Unknown names and automata that are already on a device: ACGPU_ERR_INVALID_ARGUMENT. */
 acgpu_status acgpu_set_variant(acgpu_automaton* aut, const char* name, int32_t value);
 
@@ -227,6 +228,30 @@ acgpu_status acgpu_count_patterns(acgpu_automaton* aut, const acgpu_input* input
                                   size_t shard_begin, size_t shard_end,
                                   uint64_t* counts, size_t n_counts, uint32_t flags,
                                   uint64_t* total, acgpu_profile* prof);
+
+/* Batched find (no reference counterpart; what `for s in 0..n: out[s] = ac.try_find(Input::new(H).span(off[s]..off[s+1])
+ * .anchored(a).earliest(e))` computes): the first match of EVERY segment of a packed haystack in one call.  For the haystack
+ * H that `input` describes and offsets[0..n_segments] (non-decreasing, offsets[n_segments] <= haystack_len), segment s is
+ * H[offsets[s] .. offsets[s+1]) and out[s] is exactly what AhoCorasick::try_find (src/ahocorasick.rs:1021-1028 ->
+ * src/automaton.rs:1259-1420) returns for that span on this automaton -- any MatchKind, StartKind, automaton kind and case
+ * folding; an empty pattern matches (offsets[s], offsets[s]), also in an empty segment; nothing outside a segment
+ * influences its result (no occurrence straddles two segments, no match in one suppresses one in the next).
+ *   out[s].start / .end are offsets into H; no match: out[s].pattern == ACGPU_NO_MATCH with start = end = 0.
+ *   input: haystack, haystack_len, anchored, earliest, stream, haystack_on_device and out_on_device keep their meaning;
+ *     span_start / span_end are ignored (the offsets are the spans).  `offsets` live where the haystack lives (host memory,
+ *     or device memory when input->haystack_on_device); `out` holds n_segments records, host memory or device memory
+ *     when input->out_on_device.
+ *   Errors are decided once per call, as the reference decides them per search (ACGPU_ERR_INVALID_INPUT_ANCHORED /
+ *     _UNANCHORED); NULL offsets or out with n_segments > 0, and offsets that decrease or pass haystack_len:
+ *     ACGPU_ERR_INVALID_ARGUMENT with the reason in acgpu_last_error() (`out` is then unspecified).  n_segments == 0: ACGPU_OK,
+ *     the device is not touched.
+ * One segment per wavefront lane walks the reference's try_find loop from the automaton's own start state;
+ * segments longer than variant batch_lane_max are served by acgpu_find on their span.  Synchronous.  prof: ms_scan the walk,
+ * ms_compact the classification in front of it, n_chunks the wave tasks, n_active_chunks the segments handed to acgpu_find,
+ * n_matches the segments with a match, engine_used the stepper (LDS_WALK: the DFA as u16 rows in LDS). */
+#define ACGPU_NO_MATCH 0xFFFFFFFFu
+acgpu_status acgpu_find_batch(acgpu_automaton* aut, const acgpu_input* input, const uint64_t* offsets, size_t n_segments,
+                              acgpu_match* out, acgpu_profile* prof);
 
 /* Enqueue-only form of acgpu_find_overlapping_shard for pipelined callers (no reference counterpart): haystack,
  * `out` and `totals` are device memory; the call returns as soon as the kernels are enqueued on input->stream, so a

@@ -331,6 +331,16 @@ public:
                                uint64_t* total = nullptr, acgpu_profile* prof = nullptr) const {
         detail::check(acgpu_count_patterns(h_.get(), &in, shard_begin, shard_end, dev_counts, patterns_len(), accumulate ? ACGPU_COUNT_ACCUMULATE : 0u, total, prof));
     }
+    // first match of every segment input.haystack[offsets[s] .. offsets[s+1]) (acgpu_find_batch; the span of `input` is ignored):
+    // one record per segment, pattern == ACGPU_NO_MATCH where a segment has none.  Host offsets for a host haystack, device
+    // offsets for a device haystack; the records are returned in host memory
+    std::vector<acgpu_match> find_batch(const Input& input, const uint64_t* offsets, size_t n_segments, acgpu_profile* prof = nullptr) const {
+        acgpu_input in = input.raw();
+        in.out_on_device = 0;
+        std::vector<acgpu_match> out(n_segments);
+        detail::check(acgpu_find_batch(h_.get(), &in, offsets, n_segments, out.data(), prof));
+        return out;
+    }
     // an engine variant of this automaton (acgpu_set_variant; tests and A/B runs): before its first search
     void set_variant(const char* name, int32_t value) { detail::check(acgpu_set_variant(h_.get(), name, value)); }
 

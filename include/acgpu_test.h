@@ -54,6 +54,13 @@ acgpu_status acgpu_test_engine_plan(const uint64_t* facts, const int32_t* hints,
  * variant count_hist}; else from the automaton as uploaded to the current device (facts ignored; needs a GPU). */
 acgpu_status acgpu_test_count_plan(acgpu_automaton* aut, const uint64_t* facts, uint32_t* out);
 
+/* Test hook, not a search path: which stepper acgpu_find_batch walks with (plan_batch, aho-corasick_amd/csrc/host/engine_plan.hpp):
+ * out[0] = 3 the DFA as u16 rows in LDS | 1 the global DFA | 2 the global contiguous NFA; out[1] = the staging tile in bytes,
+ * out[2] = the default of variant batch_lane_max, out[3] = the most row entries the LDS image takes.  aut == NULL: from
+ * explicit facts[0..3] = {device holds a DFA, its states, its byte classes, variant batch_rows}; else from the automaton as
+ * uploaded to the current device (facts ignored; needs a GPU). */
+acgpu_status acgpu_test_batch_plan(acgpu_automaton* aut, const uint64_t* facts, uint32_t* out);
+
 /* Test hook, not a search path: the sizing rules of the overlapping search (aho-corasick_amd/csrc/host/ov_sizes.hpp) on
  * explicit integers; out: three words.
  *   rule 0: event-list capacity of a span of `a` bytes -> out[0].
