@@ -665,6 +665,21 @@ class AhoCorasick:
         return host if out is None else out
 
     BATCH_TILE_BYTES = 8192   # kBatchTile (csrc/host/engine_plan.hpp): the walk's staging tile per wavefront
+    BATCH_ITER_STAGE = 128    # kBatchIterStage: records of a wave task (64 segments) that find_iter_batch puts together in LDS
+
+    def _batch_offsets(self, ref, offsets):
+        """(keep-alive, pointer, number of segments) of the offsets of a batched call, which live where the haystack lives."""
+        if ref.on_device:
+            import torch
+            if not (_is_torch(offsets) and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64):
+                raise TypeError("a device haystack needs a contiguous CUDA int64 offsets tensor")
+            return offsets, offsets.data_ptr(), max(int(offsets.numel()) - 1, 0)
+        keep_off = np.ascontiguousarray(offsets)
+        if keep_off.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)) or keep_off.ndim != 1:
+            raise TypeError("a host haystack needs a one-dimensional numpy uint64 or int64 offsets array")
+        if keep_off.dtype == np.int64 and keep_off.size and int(keep_off.min()) < 0:
+            raise ValueError("negative offset")
+        return keep_off, keep_off.ctypes.data, max(int(keep_off.size) - 1, 0)
 
     def find_batch(self, haystack, offsets, anchored=False, earliest=False, out=None, profile=None):
         """First match of every segment of a packed haystack (acgpu_find_batch): segment s is haystack[offsets[s]:offsets[s+1]]
@@ -674,19 +689,7 @@ class AhoCorasick:
         zero-copy on torch's current stream.  With out= a CUDA uint8 tensor of at least 24 bytes per segment the records stay on
         the device and `out` is returned."""
         ref = _HayRef(haystack)
-        if ref.on_device:
-            import torch
-            if not (_is_torch(offsets) and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64):
-                raise TypeError("a device haystack needs a contiguous CUDA int64 offsets tensor")
-            keep_off, optr, n_off = offsets, offsets.data_ptr(), int(offsets.numel())
-        else:
-            keep_off = np.ascontiguousarray(offsets)
-            if keep_off.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)) or keep_off.ndim != 1:
-                raise TypeError("a host haystack needs a one-dimensional numpy uint64 or int64 offsets array")
-            if keep_off.dtype == np.int64 and keep_off.size and int(keep_off.min()) < 0:
-                raise ValueError("negative offset")
-            optr, n_off = keep_off.ctypes.data, int(keep_off.size)
-        n = max(n_off - 1, 0)
+        keep_off, optr, n = self._batch_offsets(ref, offsets)
         stream = _device_call_stream(ref, None)
         if out is not None:
             import torch
@@ -705,6 +708,53 @@ class AhoCorasick:
         if rc:
             _raise(rc)
         return host if out is None else out
+
+    def find_iter_batch(self, haystack, offsets, anchored=False, earliest=False, overlapping=False, out=None, rec_offsets=None,
+                        profile=None):
+        """Every match of every segment of a packed haystack (acgpu_find_iter_batch), as CSR: the records of segment s =
+        haystack[offsets[s]:offsets[s+1]] are records[rec_off[s]:rec_off[s+1]], what find_iter (overlapping=True:
+        find_overlapping_iter, Standard automata) yields for that span; positions are offsets into `haystack`.  Host inputs
+        (as find_batch takes them) return (records: MATCH_DTYPE array, rec_off: uint64 array of len(offsets)).  With out= a
+        CUDA uint8 tensor and rec_offsets= a CUDA int64 tensor of len(offsets) elements, a CUDA haystack with CUDA offsets is
+        searched zero-copy on torch's current stream and both results stay on the device: returns (n_records, ok), ok =
+        False when `out` holds fewer than n_records records (nothing usable was written to it)."""
+        ref = _HayRef(haystack)
+        keep_off, optr, n = self._batch_offsets(ref, offsets)
+        on_dev = out is not None or rec_offsets is not None
+        stream = _device_call_stream(ref, None)
+        if on_dev:
+            import torch
+            if not (_is_torch(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8):
+                raise TypeError("out must be a contiguous CUDA uint8 tensor")
+            if not (_is_torch(rec_offsets) and rec_offsets.is_cuda and rec_offsets.is_contiguous() and
+                    rec_offsets.dtype == torch.int64 and rec_offsets.numel() >= n + 1):
+                raise TypeError(f"rec_offsets must be a contiguous CUDA int64 tensor of at least {n + 1} elements")
+            if stream is None:
+                stream = torch.cuda.current_stream().cuda_stream or None
+        ci = _lib.CInput(ref.ptr, ref.n, 0, ref.n, int(bool(anchored)), int(bool(earliest)), ref.on_device, int(on_dev), stream)
+        prof = None if profile is None else C.byref(profile)
+        nout = C.c_size_t()
+        if on_dev:
+            rc = self._L.acgpu_find_iter_batch(self._h, C.byref(ci), C.c_void_p(optr), n, int(bool(overlapping)),
+                                               C.c_void_p(rec_offsets.data_ptr()), C.c_void_p(out.data_ptr()),
+                                               out.numel() // MATCH_DTYPE.itemsize, C.byref(nout), prof)
+            if rc == 21:  # ACGPU_ERR_BUFFER_TOO_SMALL
+                return nout.value, False
+            if rc:
+                _raise(rc)
+            return nout.value, True
+        rec_off = np.zeros(n + 1, dtype=np.uint64)
+        cap = max(4096, 2 * n)
+        while True:   # a too-small buffer costs the count pass again (the C ABI reports the required size)
+            buf = np.empty(cap, dtype=MATCH_DTYPE)
+            rc = self._L.acgpu_find_iter_batch(self._h, C.byref(ci), C.c_void_p(optr), n, int(bool(overlapping)),
+                                               C.c_void_p(rec_off.ctypes.data), C.c_void_p(buf.ctypes.data), cap, C.byref(nout), prof)
+            if rc == 21:
+                cap = nout.value
+                continue
+            if rc:
+                _raise(rc)
+            return buf[:nout.value], rec_off
 
     def overlapping_device(self, hay_tensor, span=None, shard=None, out=None, profile=None, stream=None):
         """Device-to-device form: `hay_tensor` and `out` are torch CUDA tensors; returns the number of matches.

@@ -22,11 +22,15 @@ BatchFacts batch_facts(const DeviceState* ds) {
     return f;
 }
 
+std::string batch_bad_offsets_text(uint64_t seg) {
+    return "offsets[" + std::to_string(seg + 1) + "] is below offsets[" + std::to_string(seg) + "] or beyond haystack_len";
+}
+
 }  // namespace acgpu_capi
 
 namespace {
 
-constexpr size_t kListHead = 1024;   // entries of the long-segment list that arrive with the control words
+constexpr size_t kListHead = kBatchListHead;
 
 acgpu_status bad_argument(const std::string& why) {
     g_last_error = "acgpu_find_batch: " + why;
@@ -34,7 +38,7 @@ acgpu_status bad_argument(const std::string& why) {
 }
 
 acgpu_status bad_offsets(uint64_t seg) {
-    return bad_argument("offsets[" + std::to_string(seg + 1) + "] is below offsets[" + std::to_string(seg) + "] or beyond haystack_len");
+    return bad_argument(batch_bad_offsets_text(seg));
 }
 
 }  // namespace

@@ -18,6 +18,7 @@
 #include "acgpu.h"
 #include "capi_internal.hpp"
 #include "device/batch_find.hpp"
+#include "device/batch_iter.hpp"
 #include "device/cnfa_walk.hpp"
 #include "device/cnfa_tri.hpp"
 #include "device/cnfa_tri_step.hpp"
@@ -379,8 +380,10 @@ EngineFacts engine_facts(const acgpu_automaton* aut, const DeviceState* ds);
 acgpu_status enqueue_impl(acgpu_automaton* aut, const acgpu_input* in, size_t shard_begin, size_t shard_end, acgpu_match* out,
                           size_t cap, uint64_t* totals, int32_t slot, uint32_t flags, bool* probed, EnqueueGuess* guess = nullptr,
                           EnqueueSync* sync = nullptr);
-// ---- capi_batch.cpp
+// ---- capi_batch.cpp (shared with the batched iterator, capi_batch_iter.cpp)
 BatchFacts batch_facts(const DeviceState* ds);
+constexpr size_t kBatchListHead = 1024;   // entries of the long-segment list that arrive with the control words (Scratch::bpin)
+std::string batch_bad_offsets_text(uint64_t seg);   // offsets[seg + 1] decreases or passes the haystack
 // ---- capi_find.cpp
 acgpu_status serial_impl(acgpu_automaton* aut, const acgpu_input* in, bool single, acgpu_match* out, size_t cap,
                          size_t* n_out, acgpu_profile* prof);

@@ -15,13 +15,14 @@
 //
 // Records.  The 64 records of a task are 1 536 contiguous bytes: they are put together in the wave's tile and stored as such.
 //
-// Steppers (one skeleton, a template parameter): the LDS rows of host/batch_tables.hpp -- one class lookup and one
-// ds_read_u16 per byte --, DfaEng and CnfaEng on the global tables; all read the segment bytes from the same tile.
+// Steppers (one skeleton, a template parameter; batch_step.hpp): the LDS rows of host/batch_tables.hpp -- one class lookup
+// and one ds_read_u16 per byte --, DfaEng and CnfaEng on the global tables; all read the segment bytes from the same tile.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "batch_find.hpp"
+#include "batch_step.hpp"
 #include "host/engine_plan.hpp"
 #include "launch_util.hpp"
 #include "tile_walk.hpp"
@@ -30,64 +31,12 @@ namespace acgpu {
 
 namespace {
 
+using namespace batchdev;   // the steppers: batch_step.hpp
+
 constexpr uint32_t kBfTile = kBatchTile, kBfWaves = kBatchWaves, kBfBlock = kBatchWaves * 64;
 constexpr uint32_t kBfClsOff = kBfWaves * kBfTile, kBfRowsOff = kBfClsOff + 256;
 static_assert(kBfRowsOff + 2 * kBatchRowsMaxEntries <= kBatchLdsBytes, "the largest image fits beside the tiles");
 static_assert(64 * sizeof(acgpu_match) <= kBfTile && kBfTile % 1024 == 0, "a task's records are staged in its tile");
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t t = __shfl_xor(v, o, 64);
-        v = t < v ? t : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t t = __shfl_xor(v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
-// ---- steppers: start / next / is_special / is_match as the engines of engines.hpp, + the first pattern of a match state
-template <class E>
-struct GlobalStep {
-    E eng;
-    __device__ __forceinline__ void bind(const uint8_t* lds, const uint8_t* cls) { eng.cls = cls; }
-    __device__ __forceinline__ uint32_t image_bytes() const { return 0; }
-    __device__ __forceinline__ const void* image() const { return nullptr; }
-    __device__ __forceinline__ const uint8_t* classes() const { return eng.cls; }
-    __device__ __forceinline__ uint32_t start(bool anchored) const { return eng.start(anchored); }
-    __device__ __forceinline__ uint32_t next(bool anchored, uint32_t sid, uint8_t byte) const { return eng.next(anchored, sid, byte); }
-    __device__ __forceinline__ bool is_special(uint32_t sid) const { return eng.is_special(sid); }
-    __device__ __forceinline__ bool is_match(uint32_t sid) const { return eng.is_match(sid); }
-    __device__ __forceinline__ void first(uint32_t sid, uint32_t& pid, uint32_t& plen) const {
-        pid = eng.match_pattern(sid, 0);
-        plen = eng.pattern_len(pid);
-    }
-};
-
-struct RowsStep {
-    BatchRows t;
-    const uint16_t* rows;   // LDS
-    const uint8_t* cls;     // LDS
-    __device__ __forceinline__ void bind(const uint8_t* lds, const uint8_t* c) { rows = reinterpret_cast<const uint16_t*>(lds); cls = c; }
-    __device__ __forceinline__ uint32_t image_bytes() const { return t.rows_bytes; }
-    __device__ __forceinline__ const void* image() const { return t.rows; }
-    __device__ __forceinline__ const uint8_t* classes() const { return t.classes; }
-    __device__ __forceinline__ uint32_t start(bool anchored) const { return anchored ? t.start_anchored : t.start_unanchored; }
-    __device__ __forceinline__ uint32_t next(bool, uint32_t off, uint8_t byte) const { return rows[off + cls[byte]]; }
-    __device__ __forceinline__ bool is_special(uint32_t off) const { return off <= t.max_special; }
-    __device__ __forceinline__ bool is_match(uint32_t off) const { return off != kDevDead && off <= t.max_match; }
-    __device__ __forceinline__ void first(uint32_t off, uint32_t& pid, uint32_t& plen) const {
-        const uint2 v = *reinterpret_cast<const uint2*>(t.first + 2 * (off / t.alphabet_len - 2));
-        pid = v.x;
-        plen = v.y;
-    }
-};
 
 __global__ void k_batch_init(unsigned long long* ctl) {
     if (threadIdx.x == 0) { ctl[0] = ~0ull; ctl[1] = 0; ctl[2] = 0; }

@@ -20,12 +20,20 @@ bool build_batch_image(const Dfa& d, const std::vector<uint32_t>& pattern_lens, 
             img.rows[i * alen + c] = uint16_t(off_of(next));
         }
     img.first.assign(2 * d.num_match_states, 0);
+    img.list_off.assign(2 * d.num_match_states, 0);
     for (size_t m = 0; m < d.num_match_states; m++) {
         if (d.moff[m + 1] == d.moff[m]) return false;   // (a match state reports at least one pattern)
         const uint32_t pid = d.mpid[d.moff[m]];
         if (pid >= pattern_lens.size()) return false;
         img.first[2 * m] = pid;
         img.first[2 * m + 1] = pattern_lens[pid];
+        img.list_off[2 * m] = uint32_t(img.list.size() / 2);
+        img.list_off[2 * m + 1] = d.moff[m + 1] - d.moff[m];
+        for (uint32_t i = d.moff[m]; i < d.moff[m + 1]; i++) {
+            if (d.mpid[i] >= pattern_lens.size()) return false;
+            img.list.push_back(d.mpid[i]);
+            img.list.push_back(pattern_lens[d.mpid[i]]);
+        }
     }
     img.start_unanchored = off_of(d.special.start_unanchored_id);
     img.start_anchored = off_of(d.special.start_anchored_id);
@@ -43,6 +51,8 @@ hipError_t upload_batch_tables(const Dfa& d, const std::vector<uint32_t>& patter
     if (!want_rows || !build_batch_image(d, pattern_lens, img)) return hipSuccess;
     if (hipError_t e = out.rows.upload(img.rows); e != hipSuccess) return e;
     if (hipError_t e = out.first.upload(img.first); e != hipSuccess) return e;
+    if (hipError_t e = out.list_off.upload(img.list_off); e != hipSuccess) return e;
+    if (hipError_t e = out.list.upload(img.list); e != hipSuccess) return e;
     out.rows_bytes = uint32_t(img.rows.size() * sizeof(uint16_t));
     out.start_unanchored = img.start_unanchored; out.start_anchored = img.start_anchored;
     out.max_special = img.max_special; out.max_match = img.max_match;

@@ -85,6 +85,19 @@ inline BatchForm plan_batch(const BatchFacts& f) {
     return f.has_dfa ? BatchForm::DfaWalk : BatchForm::CnfaWalk;
 }
 
+// Which stepper the batched iterator walks with (acgpu_find_iter_batch, capi_batch_iter.cpp / device/batch_iter.hip): plan_batch's
+// answer, except that its fill pass keeps kBatchIterStage records per wavefront in LDS beside the tiles (a task's records
+// are put together there and stored as one piece), so the rows form is chosen only when the image fits what that leaves of
+// the 160 KiB; an automaton between the two limits walks the global DFA.
+constexpr uint32_t kBatchIterStage = 128;                                        // records (24 bytes each) per wavefront
+constexpr uint32_t kBatchIterStageBytes = kBatchWaves * kBatchIterStage * 24;    // 12 KiB per workgroup
+constexpr uint32_t kBatchIterRowsMaxEntries = kBatchRowsMaxEntries - kBatchIterStageBytes / 2;
+inline BatchForm plan_batch_iter(const BatchFacts& f) {
+    const BatchForm p = plan_batch(f);
+    if (p == BatchForm::LdsRows && f.dfa_states * f.alphabet_len > kBatchIterRowsMaxEntries) return BatchForm::DfaWalk;
+    return p;
+}
+
 // What the hints of the automaton make of a prefix-filter scan that has an alternative (spans of kProbeMinSpan and more,
 // and only while the first kernel is the two-type filter): take the alternative unasked, ask the probe first, or just scan.
 enum class PfStart : uint32_t { Scan = 0, Probe = 1, TakeAlternative = 2 };

@@ -253,6 +253,30 @@ acgpu_status acgpu_count_patterns(acgpu_automaton* aut, const acgpu_input* input
 acgpu_status acgpu_find_batch(acgpu_automaton* aut, const acgpu_input* input, const uint64_t* offsets, size_t n_segments,
                               acgpu_match* out, acgpu_profile* prof);
 
+/* Batched iterator (no reference counterpart; what `for s in 0..n: ac.try_find_iter(Input::new(H).span(off[s]..off[s+1])
+ * .anchored(a).earliest(e))` -- or try_find_overlapping_iter with overlapping != 0 -- yields, concatenated): EVERY match of
+ * every segment of a packed haystack in one call, as CSR.  Segments and `input` are those of acgpu_find_batch; the records of
+ * segment s are out[rec_offsets[s] .. rec_offsets[s+1]), in the iterator's order, exactly what the reference returns for that
+ * span (src/automaton.rs:857-936 with the empty-match rule :910-920 and the caller's `earliest` kept across restarts;
+ * overlapping: :1443-1534, the whole match list at every match state, `earliest` without effect); start / end are offsets
+ * into H.  rec_offsets[0] = 0, rec_offsets[n_segments] = *n_out = the total.
+ *   rec_offsets holds n_segments + 1 entries and `out` `cap` records: host memory, or BOTH device memory when
+ *     input->out_on_device.  If the total exceeds cap: ACGPU_ERR_BUFFER_TOO_SMALL with *n_out = the required capacity;
+ *     nothing is written to `out` (it may be NULL with cap 0), rec_offsets may be written.
+ *   overlapping != 0 is refused as acgpu_find_overlapping refuses it (src/automaton.rs:397-423: a leftmost automaton
+ *     ACGPU_ERR_UNSUPPORTED_OVERLAPPING, anchored input ACGPU_ERR_INVALID_INPUT_ANCHORED), like the other errors of
+ *     acgpu_find_batch before any device work (NULL arguments, bad offsets: ACGPU_ERR_INVALID_ARGUMENT with the reason in
+ *     acgpu_last_error()).  n_segments == 0: ACGPU_OK, *n_out = 0, the device is not touched: host rec_offsets[0] = 0 is
+ *     stored, device rec_offsets are left as they are.
+ * Two passes of one segment per wavefront lane -- count, prefix sum, fill; only segments with matches are walked twice --
+ * and two synchronisations; segments longer than variant batch_lane_max are served by acgpu_find_iter /
+ * acgpu_find_overlapping on their span.  The variants of acgpu_find_batch apply.  prof: ms_compact classification + count +
+ * prefix sum, ms_scan the fill, n_chunks the wave tasks, n_active_chunks the segments handed to the single-span calls,
+ * n_matches the total, engine_used the stepper; with ACGPU_ERR_BUFFER_TOO_SMALL the counts and ms_compact = ms_total. */
+acgpu_status acgpu_find_iter_batch(acgpu_automaton* aut, const acgpu_input* input, const uint64_t* offsets, size_t n_segments,
+                                   int overlapping, uint64_t* rec_offsets, acgpu_match* out, size_t cap, size_t* n_out,
+                                   acgpu_profile* prof);
+
 /* Enqueue-only form of acgpu_find_overlapping_shard for pipelined callers (no reference counterpart): haystack,
  * `out` and `totals` are device memory; the call returns as soon as the kernels are enqueued on input->stream, so a
  * caller can queue the next buffer while this one is scanned and never pays a host round trip per call.

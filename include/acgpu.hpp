@@ -341,6 +341,27 @@ public:
         detail::check(acgpu_find_batch(h_.get(), &in, offsets, n_segments, out.data(), prof));
         return out;
     }
+    // every match of every segment (acgpu_find_iter_batch), as CSR: the records of segment s are
+    // records[rec_off[s] .. rec_off[s+1]), what try_find_iter (overlapping: try_find_overlapping_iter) yields for that span
+    struct BatchMatches { std::vector<uint64_t> rec_off; std::vector<acgpu_match> records; };
+    BatchMatches find_iter_batch(const Input& input, const uint64_t* offsets, size_t n_segments, bool overlapping = false,
+                                 acgpu_profile* prof = nullptr) const {
+        acgpu_input in = input.raw();
+        in.out_on_device = 0;
+        BatchMatches r;
+        r.rec_off.assign(n_segments + 1, 0);
+        r.records.resize(4096);
+        size_t n = 0;
+        for (;;) {
+            const int rc = acgpu_find_iter_batch(h_.get(), &in, offsets, n_segments, overlapping ? 1 : 0, r.rec_off.data(), r.records.data(),
+                                                 r.records.size(), &n, prof);
+            if (rc == ACGPU_ERR_BUFFER_TOO_SMALL) { r.records.resize(n); continue; }
+            detail::check(rc);
+            break;
+        }
+        r.records.resize(n);
+        return r;
+    }
     // an engine variant of this automaton (acgpu_set_variant; tests and A/B runs): before its first search
     void set_variant(const char* name, int32_t value) { detail::check(acgpu_set_variant(h_.get(), name, value)); }
 
