@@ -11,6 +11,8 @@ namespace pfdev {
 constexpr int kPfBlock = 1024;
 constexpr int kPfWaves = kPfBlock / 64;
 constexpr int kQueue = 128;           // per-wave survivor queues (drained in batches of 64)
+constexpr int kDeferWords = 6;        // deferred level-1 survivors (pf_scan.hip: PfWave::defer): {hit mask | row offset << 8, the row's five dwords}
+constexpr int kDeferCap = 92;         // ... entries per wave: a batch of 64 + the hit lanes of three to four typical row pairs
 constexpr int kEvBuf = 48;            // per-wave LDS event buffer (event modes), flushed from kEvFlush entries on
 constexpr int kEvFlush = 24;
 constexpr uint32_t kRowBytes = 1008;  // one wave-row: 63 lanes x 16 B of start positions (lane 63 only supplies
@@ -21,7 +23,7 @@ constexpr uint32_t kBitsBytes = 64 * 1024;  // level-1 Bloom table (static LDS a
 
 struct PfArgs {
     const uint32_t* bits;   // level-1 Bloom table (global copy)
-    const uint32_t* bits2;  // second Bloom table (global copy), kPfBits2Bytes
+    const uint32_t* bits2;  // second Bloom table (global copy), pf_bits2_bytes()
     const uint32_t* atab;   // trie-only transitions, class-compressed: [state][1 << ashift]
     const uint8_t* acls;    // its class map (global copy; the kernels stage it into LDS)
     uint32_t ashift;

@@ -11,14 +11,21 @@
 //       every pattern twice (hot.hpp / host/pf_tables.cpp) -- "type 0" = bytes 1..3 as key, byte 0 selects the bit, tested
 //       with b[q]; "type 1" = bytes 0..2 as key, byte 3 selects the bit, tested with b[q+4].  ~0.77 % of the even
 //       positions of a random haystack survive for the 1k-pattern set, almost all Bloom false positives.
-//   survivors  (0.77 % of the probes) each lane peels its survivor bits, takes the window b[q..q+4] from its row
-//       registers (the haystack is never re-read) and probes a SECOND, independently hashed 64 KiB Bloom table.
-//       Up to 24 000 patterns that table has the construction of the first one and the probe is repeated under the
-//       other hash (one gather; a false positive of the first table survives with the fill of the second, 0.8 %, and
-//       both starts the probe stands for go on); for larger sets (HotTables::pf_exact2, kernel instance X2) it holds
-//       one entry per pattern keyed by the true start and is probed once per candidate start (q: key b[q..q+2], bit
-//       b[q+3]; q+1: key b[q+1..q+3], bit b[q+4]).  What is left -- ~0.03 probes per 1008-byte row on the headline
-//       input, almost all true 4-byte prefix matches -- goes straight to level 3.
+//   survivors  (0.77 % of the probes: ~8 per row pair and wavefront, in ~7 of its 64 lanes)  a survivor's window
+//       b[q..q+4] comes from its lane's row registers (the haystack is never re-read) and probes a SECOND, independently
+//       hashed Bloom table.  Up to 24 000 patterns that table (32 KiB) has the construction of the first one and the
+//       probe is repeated under the other hash (one gather; a false positive of the first table survives with the fill
+//       of the second, and both starts the probe stands for go on); for larger sets (HotTables::pf_exact2, kernel
+//       instance X2) it holds one entry per pattern keyed by the true start (64 KiB) and is probed once per candidate
+//       start (q: key b[q..q+2], bit b[q+3]; q+1: key b[q+1..q+3], bit b[q+4]).  What is left -- 0.12 probes per
+//       1008-byte row on the headline input (host model, host/pf_tables.cpp: 3.84 level-1 survivors per row, 3.2 % of
+//       them pass; 0.10 with a 64 KiB table) -- goes straight to level 3.
+//       The row path does not peel the survivor bits: a lane with hits appends one entry per row {hit mask, row offset,
+//       the row's five dwords} to a per-wavefront LDS queue (PfWave::defer), and 64 waiting entries are peeled as a
+//       dense batch (drain_deferred), every lane active on the first trip.  Peeling in the row path executed ~40 VALU
+//       instructions per trip for the ~7 lanes that had something to do, in essentially every row pair.  Row pairs whose
+//       hit lanes do not fit the queue (hit-dense input) and the X2 instances (their table leaves no LDS for the queue)
+//       are peeled in the row path (PfWave::survivors).
 //   level 3  (dense batches of 64 from a per-wavefront LDS queue filled at __ballot/mbcnt ranks)   exact walk of the
 //       trie-only (anchored) transition table in global memory from the start state.  Every pattern end is credited
 //       to the chunk owning it (classic mode, counts for the scan + fill pipeline) or recorded as an event
@@ -70,6 +77,9 @@ struct PfWave {
     PfEvent* ebuf;       // per-wave event buffer + its fill counter (event modes)
     uint32_t* ecnt;
     uint32_t* rt;        // per-wave routing counters (LDS): [0] level-3 starts, [1] events flushed, [2] tasks started, [3] abandoned
+    uint32_t* dq;        // deferred level-1 survivors: kDeferCap entries of kDeferWords dwords (nullptr for X2: no LDS left)
+    uint32_t dcount = 0;     // wave-uniform fill level of dq; entries never outlive the task they were queued in
+    static constexpr uint32_t kB2Bytes = pf_bits2_bytes(X2);
     uint64_t task_base = 0;
     uint32_t q2count = 0;    // wave-uniform fill level; a batch = the LAST (up to) 64 entries (order is irrelevant)
     uint32_t xcount = 0;     // wave-uniform: starts handed to level 3 so far (the probe's measure)
@@ -218,11 +228,36 @@ struct PfWave {
         return __builtin_amdgcn_alignbit(hi, mid ? c1 : c0, 8u * (k & 3u));
     }
 
-    // level-1 survivors of a pair of rows.  Each lane that has one peels its lowest survivor q, takes the window
-    // b[q..q+4] from its row registers (the haystack is never re-read) and repeats the level-1 probe in the SECOND,
+    // One level-1 survivor: offset q (odd) of the row `wd` whose byte 0 is start position `pos`.  The window b[q..q+4]
+    // comes from the row registers (the haystack is never re-read) and repeats the level-1 probe in the SECOND,
     // independently hashed Bloom table.  A false positive of the first table survives with the fill of the second
-    // (0.8 %): what is left (~0.03 probes per row on the headline input, almost all true 4-byte prefix matches) hands
-    // both start positions it stands for to the exact trie walk of level 3.
+    // (X2: an exact 64 KiB table): what is left (0.12 probes per row on the headline input)
+    // hands both start positions it stands for to the exact trie walk of level 3.
+    __device__ __forceinline__ void level2(bool has, const uint32_t (&wd)[5], uint32_t q, uint64_t pos) {
+        uint32_t next;
+        const uint32_t win = window(wd, q, next);
+        // the same probe as level 1 (key b[q+1..q+3], bits selected by b[q] and b[q+4]) in the second table
+        bool ok_a, ok_b;
+        if (X2) {   // the two exact candidate starts (q: key b[q..q+2], bit b[q+3]; q+1: key b[q+1..q+3], bit b[q+4])
+            const uint32_t wa = s_bits2[(pf_hash2(win) & (kB2Bytes - 4)) >> 2];
+            const uint32_t wb = s_bits2[(pf_hash2(win >> 8) & (kB2Bytes - 4)) >> 2];
+            ok_a = has && int32_t(wa << ((win >> 24) & 31)) < 0;
+            ok_b = has && int32_t(wb << (next & 31)) < 0;
+        } else {
+            const uint32_t w2 = s_bits2[(pf_hash2(win >> 8) & (kB2Bytes - 4)) >> 2];
+            const bool ok = has && int32_t((w2 << (win & 31)) | (w2 << (next & 31))) < 0;
+            ok_a = ok; ok_b = ok;   // either start may be the one: level 3 verifies both
+        }
+        if (__any(ok_a | ok_b)) {
+            const uint64_t v = pos + q;
+            push_q2(ok_a && v >= a.scan_lo && v < g.emit_hi, v);
+            push_q2(ok_b && v + 1 >= a.scan_lo && v + 1 < g.emit_hi, v + 1);
+        }
+    }
+
+    // level-1 survivors of a pair of rows, in the row path: each lane that has one peels its lowest survivor bit and
+    // takes it through level2.  ~40 VALU instructions per trip for the ~7 lanes of 64 that hold a survivor: X2 (no LDS
+    // for the queue below) and row pairs whose hit lanes do not fit the queue (hit-dense input) take this form.
     __device__ __forceinline__ void survivors(uint32_t hits, const uint32_t (&w0)[5], const uint32_t (&w1)[5], uint32_t off) {
         while (__any(hits != 0)) {
             const bool has = hits != 0;
@@ -231,26 +266,51 @@ struct PfWave {
             const bool second = (i & 8u) != 0;
             const uint32_t wd[5] = {second ? w1[0] : w0[0], second ? w1[1] : w0[1], second ? w1[2] : w0[2],
                                     second ? w1[3] : w0[3], second ? w1[4] : w0[4]};
-            const uint32_t q = (i & 7u) * 2u + 1u;
-            uint32_t next;
-            const uint32_t win = window(wd, q, next);
-            // the same probe as level 1 (key b[q+1..q+3], bits selected by b[q] and b[q+4]) in the second table
-            bool ok_a, ok_b;
-            if (X2) {   // the two exact candidate starts (q: key b[q..q+2], bit b[q+3]; q+1: key b[q+1..q+3], bit b[q+4])
-                const uint32_t wa = s_bits2[(pf_hash2(win) & (kPfBits2Bytes - 4)) >> 2];
-                const uint32_t wb = s_bits2[(pf_hash2(win >> 8) & (kPfBits2Bytes - 4)) >> 2];
-                ok_a = has && int32_t(wa << ((win >> 24) & 31)) < 0;
-                ok_b = has && int32_t(wb << (next & 31)) < 0;
-            } else {
-                const uint32_t w2 = s_bits2[(pf_hash2(win >> 8) & (kPfBits2Bytes - 4)) >> 2];
-                const bool ok = has && int32_t((w2 << (win & 31)) | (w2 << (next & 31))) < 0;
-                ok_a = ok; ok_b = ok;   // either start may be the one: level 3 verifies both
-            }
-            if (__any(ok_a | ok_b)) {
-                const uint64_t v = task_base + off + (second ? kRowBytes : 0u) + q;
-                push_q2(ok_a && v >= a.scan_lo && v < g.emit_hi, v);
-                push_q2(ok_b && v + 1 >= a.scan_lo && v + 1 < g.emit_hi, v + 1);
-            }
+            level2(has, wd, (i & 7u) * 2u + 1u, task_base + off + (second ? kRowBytes : 0u));
+        }
+    }
+
+    // The same survivors, deferred: a lane whose row has survivor bits appends ONE entry per row -- {the row's 8-bit hit
+    // mask | its offset in the task << 8, the row's five dwords} -- to the wave's LDS queue at its __ballot / mbcnt rank and
+    // goes on with the next pair; nothing is peeled here.  64 waiting entries are drained as a dense batch (drain_deferred:
+    // every lane active on the first trip, where the loop above runs for ~7).  The queue is empty at every task seam.
+    static __device__ __forceinline__ uint32_t rank_in(unsigned long long m) {
+        return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
+    }
+    __device__ __forceinline__ void defer_row(bool has, uint32_t slot, uint32_t hdr, const uint32_t (&wd)[5]) {
+        if (has) {
+            uint2* e = reinterpret_cast<uint2*>(dq + slot * kDeferWords);
+            e[0] = make_uint2(hdr, wd[0]); e[1] = make_uint2(wd[1], wd[2]); e[2] = make_uint2(wd[3], wd[4]);
+        }
+    }
+    __device__ __forceinline__ void defer(uint32_t hits, const uint32_t (&w0)[5], const uint32_t (&w1)[5], uint32_t off) {
+        const bool h0 = (hits & 0xFF00u) != 0, h1 = (hits & 0xFFu) != 0;
+        const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1);
+        const uint32_t n0 = uint32_t(__popcll(m0)), n = n0 + uint32_t(__popcll(m1));
+        if (n == 0) return;
+        if (dcount + n > uint32_t(kDeferCap)) { survivors(hits, w0, w1, off); return; }   // (wave-uniform)
+        defer_row(h0, dcount + rank_in(m0), (hits >> 8) | (off << 8), w0);
+        defer_row(h1, dcount + n0 + rank_in(m1), (hits & 0xFFu) | ((off + kRowBytes) << 8), w1);
+        dcount += n;
+        if (dcount >= 64) drain_deferred(64);
+    }
+    // lane k takes the k-th of the last n entries (order is irrelevant) through the peel loop
+    __device__ __forceinline__ void drain_deferred(uint32_t n) {
+        pf_fence();
+        dcount -= n;
+        uint2 e0 = make_uint2(0, 0), e1 = e0, e2 = e0;
+        if (uint32_t(lane) < n) {
+            const uint2* e = reinterpret_cast<const uint2*>(dq + (dcount + uint32_t(lane)) * kDeferWords);
+            e0 = e[0]; e1 = e[1]; e2 = e[2];
+        }
+        const uint32_t wd[5] = {e0.y, e1.x, e1.y, e2.x, e2.y};
+        const uint64_t pos = task_base + (e0.x >> 8);
+        uint32_t hits = e0.x & 0xFFu;   // bit 7-j <=> offset q = 2 j + 1
+        while (__any(hits != 0)) {
+            const bool has = hits != 0;
+            const uint32_t j = (7u - uint32_t(__builtin_ctz(hits | 0x100u))) & 7u;
+            hits &= hits - 1;
+            level2(has, wd, j * 2u + 1u, pos);
         }
     }
 
@@ -306,7 +366,9 @@ struct PfWave {
             const uint32_t w1[5] = {wb.x | fm, wb.y | fm, wb.z | fm, wb.w | fm, uint32_t(__builtin_amdgcn_update_dpp(0, int(wb.x), 0x130, 0xF, 0xF, false)) | fm};
             uint32_t hits = level1_pair(w0, w1);
             if (lane == 63) hits = 0;  // lane 63's 16 bytes are lane 0 of the next row
-            survivors(hits, w0, w1, off);  // (start positions outside [scan_lo, emit_hi) are dropped before level 3)
+            // (start positions outside [scan_lo, emit_hi) are dropped before level 3)
+            if (X2) survivors(hits, w0, w1, off);
+            else defer(hits, w0, w1, off);
             p += 2 * kRowBytes;
             off += 2 * kRowBytes;
         };
@@ -339,8 +401,22 @@ struct PfWave {
             }
         }
         carried = completed && next_interior;
+        while (dcount) drain_deferred(dcount < 64 ? dcount : 64);   // (entries hold offsets into THIS task)
     }
 };
+
+// dynamic LDS of both kernels: [second table | q2 | event buffers, their counters, routing counters | deferred survivors]
+constexpr size_t pf_smem_bytes(bool x2) {
+    return size_t(pf_bits2_bytes(x2)) + size_t(kPfWaves) * kQueue * sizeof(uint64_t) +
+           size_t(kPfWaves) * (kEvBuf * sizeof(PfEvent) + sizeof(uint32_t) + 4 * sizeof(uint32_t)) +
+           (x2 ? 0 : size_t(kPfWaves) * kDeferCap * kDeferWords * sizeof(uint32_t));
+}
+// (160 KiB - level-1 table - 512: the dynamic-LDS limit the launchers request, which leaves room for s_acls)
+static_assert(pf_smem_bytes(false) <= 160 * 1024 - kBitsBytes - 512 && pf_smem_bytes(true) <= 160 * 1024 - kBitsBytes - 512,
+              "dynamic LDS of one workgroup exceeds what the launchers request");
+static_assert((kDeferWords * 4) % 8 == 0 && kTaskRows * kRowBytes < (1u << 24), "deferred entries: 8-byte units, 24-bit row offsets");
+// Registers: the non-X2 instances of k_pf_count use 127 of the 128 VGPRs a 1 024-thread workgroup may have (X2: 119); check
+// -Rpass-analysis=kernel-resource-usage after any change to the row loop -- scratch must stay 0.
 
 template <bool X2, bool FOLD = false>
 __global__ __launch_bounds__(kPfBlock) void k_pf_count(PfArgs a, ScanGeom g, uint32_t* __restrict__ counts) {
@@ -348,21 +424,23 @@ __global__ __launch_bounds__(kPfBlock) void k_pf_count(PfArgs a, ScanGeom g, uin
     __shared__ __attribute__((aligned(16))) uint32_t s_bits[kBitsBytes / 4];
     __shared__ uint8_t s_acls[256];
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr uint32_t kB2 = pf_bits2_bytes(X2);
     uint32_t* s_bits2 = reinterpret_cast<uint32_t*>(smem);
-    uint64_t* s_q = reinterpret_cast<uint64_t*>(smem + kPfBits2Bytes);
-    PfEvent* s_ev = reinterpret_cast<PfEvent*>(smem + kPfBits2Bytes + size_t(kPfWaves) * kQueue * sizeof(uint64_t));
+    uint64_t* s_q = reinterpret_cast<uint64_t*>(smem + kB2);
+    PfEvent* s_ev = reinterpret_cast<PfEvent*>(smem + kB2 + size_t(kPfWaves) * kQueue * sizeof(uint64_t));
     uint32_t* s_ecnt = reinterpret_cast<uint32_t*>(s_ev + kPfWaves * kEvBuf);
     uint32_t* s_rt = s_ecnt + kPfWaves;
+    uint32_t* s_dq = s_rt + kPfWaves * 4;   // (non-X2 only: pf_smem_bytes)
     if (a.gate && *a.gate != a.gate_val) return;   // (the probe chose the other filter)
     if (threadIdx.x < kPfWaves) s_ecnt[threadIdx.x] = 0;
     if (threadIdx.x < 256) s_acls[threadIdx.x] = a.acls[threadIdx.x];
     if (threadIdx.x < kPfWaves * 4) s_rt[threadIdx.x] = 0;
     for (uint32_t i = threadIdx.x; i < kBitsBytes / 4; i += kPfBlock) s_bits[i] = a.bits[i];
-    for (uint32_t i = threadIdx.x; i < kPfBits2Bytes / 4; i += kPfBlock) s_bits2[i] = a.bits2[i];
+    for (uint32_t i = threadIdx.x; i < kB2 / 4; i += kPfBlock) s_bits2[i] = a.bits2[i];
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    PfWave<X2, FOLD> st{a, g, counts, s_bits, s_bits2, s_acls, s_q + wave * kQueue, s_ev + wave * kEvBuf, s_ecnt + wave, s_rt + wave * 4};
+    PfWave<X2, FOLD> st{a, g, counts, s_bits, s_bits2, s_acls, s_q + wave * kQueue, s_ev + wave * kEvBuf, s_ecnt + wave, s_rt + wave * 4, X2 ? nullptr : s_dq + wave * (kDeferCap * kDeferWords)};
     st.lane = lane;
     st.amask = (kBitsBytes - 1) & ~3u;
 
@@ -405,16 +483,18 @@ __global__ __launch_bounds__(kPfBlock) void k_pf_probe(PfArgs a, ScanGeom g, uin
     __shared__ __attribute__((aligned(16))) uint32_t s_bits[kBitsBytes / 4];
     __shared__ uint8_t s_acls[256];
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr uint32_t kB2 = pf_bits2_bytes(X2);
     uint32_t* s_bits2 = reinterpret_cast<uint32_t*>(smem);
-    uint64_t* s_q = reinterpret_cast<uint64_t*>(smem + kPfBits2Bytes);
-    PfEvent* s_ev = reinterpret_cast<PfEvent*>(smem + kPfBits2Bytes + size_t(kPfWaves) * kQueue * sizeof(uint64_t));
+    uint64_t* s_q = reinterpret_cast<uint64_t*>(smem + kB2);
+    PfEvent* s_ev = reinterpret_cast<PfEvent*>(smem + kB2 + size_t(kPfWaves) * kQueue * sizeof(uint64_t));
     uint32_t* s_ecnt = reinterpret_cast<uint32_t*>(s_ev + kPfWaves * kEvBuf);
     uint32_t* s_rt = s_ecnt + kPfWaves;
+    uint32_t* s_dq = s_rt + kPfWaves * 4;   // (non-X2 only: pf_smem_bytes)
     if (threadIdx.x < kPfWaves) s_ecnt[threadIdx.x] = 0;
     if (threadIdx.x < 256) s_acls[threadIdx.x] = a.acls[threadIdx.x];
     if (threadIdx.x < kPfWaves * 4) s_rt[threadIdx.x] = 0;
     for (uint32_t i = threadIdx.x; i < kBitsBytes / 4; i += kPfBlock) s_bits[i] = a.bits[i];
-    for (uint32_t i = threadIdx.x; i < kPfBits2Bytes / 4; i += kPfBlock) s_bits2[i] = a.bits2[i];
+    for (uint32_t i = threadIdx.x; i < kB2 / 4; i += kPfBlock) s_bits2[i] = a.bits2[i];
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t sample = uint64_t(blockIdx.x) * kPfWaves + wave;
@@ -431,7 +511,7 @@ __global__ __launch_bounds__(kPfBlock) void k_pf_probe(PfArgs a, ScanGeom g, uin
         lg.emit_lo = ws; lg.emit_hi = ws + kSampleBytes;
         const uint64_t he = (lg.emit_hi + 31) & ~uint64_t(15);
         la.hull_end = he < a.hull_end ? he : a.hull_end;
-        PfWave<X2, FOLD> st{la, lg, nullptr, s_bits, s_bits2, s_acls, s_q + wave * kQueue, s_ev + wave * kEvBuf, s_ecnt + wave, s_rt + wave * 4};
+        PfWave<X2, FOLD> st{la, lg, nullptr, s_bits, s_bits2, s_acls, s_q + wave * kQueue, s_ev + wave * kEvBuf, s_ecnt + wave, s_rt + wave * 4, X2 ? nullptr : s_dq + wave * (kDeferCap * kDeferWords)};
         st.lane = lane;
         st.amask = (kBitsBytes - 1) & ~3u;
         st.template run_task<true>(ws, 0, false);
@@ -540,8 +620,7 @@ hipError_t launch_pf_count(const HotTables& h, const ScanGeom& g, uint32_t* coun
     if (e != hipSuccess) return e;
     if (a.n_tasks == 0) return hipSuccess;
     if (a.bits_bytes != kBitsBytes) return hipErrorInvalidValue;
-    const size_t smem = size_t(kPfBits2Bytes) + size_t(kPfWaves) * kQueue * sizeof(uint64_t) +
-                        size_t(kPfWaves) * (kEvBuf * sizeof(PfEvent) + sizeof(uint32_t) + 4 * sizeof(uint32_t));
+    const size_t smem = pf_smem_bytes(h.pf_exact2);
     typedef void (*CountKernel)(PfArgs, ScanGeom, uint32_t*);
     const CountKernel kern = h.pf_exact2 ? (h.pf_fold ? k_pf_count<true, true> : k_pf_count<true, false>)
                                          : (h.pf_fold ? k_pf_count<false, true> : k_pf_count<false, false>);
@@ -570,8 +649,7 @@ hipError_t launch_pf_probe(const HotTables& h, const ScanGeom& g, PfRoute route,
     const uint64_t span = g.emit_hi > a.row0 ? g.emit_hi - a.row0 : 0;
     const uint64_t stride = (span / kSamples) & ~uint64_t(15);
     if (stride < uint64_t(2 * kSets) * kRowBytes) return hipErrorInvalidValue;   // (callers probe large shards only)
-    const size_t smem = size_t(kPfBits2Bytes) + size_t(kPfWaves) * kQueue * sizeof(uint64_t) +
-                        size_t(kPfWaves) * (kEvBuf * sizeof(PfEvent) + sizeof(uint32_t) + 4 * sizeof(uint32_t));
+    const size_t smem = pf_smem_bytes(h.pf_exact2);
     typedef void (*ProbeKernel)(PfArgs, ScanGeom, uint32_t, uint64_t, uint32_t, uint32_t, uint32_t*, unsigned long long*);
     const ProbeKernel kern = h.pf_exact2 ? (h.pf_fold ? k_pf_probe<true, true> : k_pf_probe<true, false>)
                                          : (h.pf_fold ? k_pf_probe<false, true> : k_pf_probe<false, false>);

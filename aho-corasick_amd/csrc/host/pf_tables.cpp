@@ -95,7 +95,7 @@ bool build_pf_host(const NNfa& n, const std::vector<uint32_t>& order, const std:
     // its bytes 1..3 are the key, its byte 0 selects the bit, tested with b[q]) or at q+1 ("type 1": its bytes
     // 0..2 are the key, its byte 3 selects the bit, tested with b[q+4]).  Patterns shorter than four bytes fill in
     // every value of the bytes they do not have.
-    // A second table of the same construction under an unrelated hash (pf_hash2, kPfBits2Bytes) is probed only for the
+    // A second table of the same construction under an unrelated hash (pf_hash2, pf_bits2_bytes()) is probed only for the
     // survivors of the first one: a false positive of one table passes the other with its fill probability.
     // Case folding of the KEYS (HotTables::pf_fold): under ascii_case_insensitive every letter edge exists twice and leads
     // to one child, so a 3-byte key has up to 8 spellings and the tables fill up accordingly (config 5: the same kernel
@@ -119,7 +119,7 @@ bool build_pf_host(const NNfa& n, const std::vector<uint32_t>& order, const std:
     // (filled after this loop), so here only the first table is written.
     const bool exact2 = n.n_patterns > kPfExact2Patterns;
     t.exact2 = exact2;
-    std::vector<uint32_t> bits(bits_bytes / 4, 0), bits2(kPfBits2Bytes / 4, 0);
+    std::vector<uint32_t> bits(bits_bytes / 4, 0), bits2(pf_bits2_bytes(exact2) / 4, 0);
     uint32_t sink = 0;
     struct TwoWords {   // the word of the key in both tables
         uint32_t &w1, &w2;
@@ -129,7 +129,7 @@ bool build_pf_host(const NNfa& n, const std::vector<uint32_t>& order, const std:
     auto word_of = [&](uint32_t b0, uint32_t b1, uint32_t b2) -> TwoWords {
         const uint32_t key = (b0 | (b1 << 8) | (b2 << 16)) | fm;
         return TwoWords{bits[(pf_hash(key) & (bits_bytes - 1)) >> 2],
-                        exact2 ? sink : bits2[(pf_hash2(key) & (kPfBits2Bytes - 1)) >> 2]};
+                        exact2 ? sink : bits2[(pf_hash2(key) & (pf_bits2_bytes(false) - 1)) >> 2]};
     };
     auto bit_of = [](uint32_t b) { return 1u << (31 - (b & 31)); };
     // third table (HBM / L2): exact first four bytes of every pattern, ~64 bits per pattern
@@ -179,7 +179,7 @@ bool build_pf_host(const NNfa& n, const std::vector<uint32_t>& order, const std:
     }
     if (exact2) {   // one entry per trie path of depth <= 4 from the start state, keyed by the true start
         auto word2_of = [&](uint32_t b0, uint32_t b1, uint32_t b2) -> uint32_t& {
-            return bits2[(pf_hash2((b0 | (b1 << 8) | (b2 << 16)) | fm) & (kPfBits2Bytes - 1)) >> 2];
+            return bits2[(pf_hash2((b0 | (b1 << 8) | (b2 << 16)) | fm) & (pf_bits2_bytes(true) - 1)) >> 2];
         };
         for (uint32_t k = n.toff[su]; k < n.toff[su + 1]; k++) {
             if (!is_trie_child(su, k)) continue;
@@ -402,12 +402,12 @@ uint64_t pf_emulate_count(const PfHostTables& t, uint32_t start_hid, const uint8
             bool ok_a, ok_b;
             if (t.exact2) {   // one entry per trie path keyed by the true start: q -> key b[q..q+2], bit b[q+3]; q+1 likewise
                 const uint32_t ka = (m.byte(q) | (m.byte(q + 1) << 8) | (m.byte(q + 2) << 16)) | fm;
-                const uint32_t wa = t.bits2[(pf_hash2(ka) & (kPfBits2Bytes - 1)) >> 2];
-                const uint32_t wb = t.bits2[(pf_hash2(key) & (kPfBits2Bytes - 1)) >> 2];
+                const uint32_t wa = t.bits2[(pf_hash2(ka) & (pf_bits2_bytes(true) - 1)) >> 2];
+                const uint32_t wb = t.bits2[(pf_hash2(key) & (pf_bits2_bytes(true) - 1)) >> 2];
                 ok_a = (wa << (m.byte(q + 3) & 31)) >> 31;
                 ok_b = (wb << (m.byte(q + 4) & 31)) >> 31;
             } else {
-                const uint32_t w2 = t.bits2[(pf_hash2(key) & (kPfBits2Bytes - 1)) >> 2];
+                const uint32_t w2 = t.bits2[(pf_hash2(key) & (pf_bits2_bytes(false) - 1)) >> 2];
                 ok_a = ok_b = ((w2 << (m.byte(q) & 31)) | (w2 << (m.byte(q + 4) & 31))) >> 31;
             }
             if (ok_a || ok_b) survivors2++;

@@ -17,7 +17,7 @@ struct PfHostTables {
     std::vector<uint32_t> atab;      // [hid << ashift | class] trie-only transitions: child hid | 1 << 31 if a pattern ends there
     std::vector<uint8_t> acls;       // [256] class map of atab (0 = byte on no trie edge)
     uint32_t ashift = 8;
-    std::vector<uint32_t> bits, bits2, bits3;   // two-type filter: first / second table (64 KiB each), exact-4-byte bit table
+    std::vector<uint32_t> bits, bits2, bits3;   // two-type filter: first / second table (64 KiB; pf_bits2_bytes(exact2)), exact-4-byte bit table
     uint32_t bits_bytes = 0, bits3_log2 = 0;
     bool exact2 = false, use3 = false;
     bool fold = false;               // two-type filter: key bytes of both tables are taken | 0x20 (case-folded automata)
