@@ -687,7 +687,10 @@ class AhoCorasick:
         NO_MATCH with start = end = 0.  Host inputs (bytes / numpy uint8 with a numpy uint64 or int64 offsets array) return a
         numpy MATCH_DTYPE array of len(offsets) - 1 records; a CUDA uint8 tensor with a CUDA int64 offsets tensor is searched
         zero-copy on torch's current stream.  With out= a CUDA uint8 tensor of at least 24 bytes per segment the records stay on
-        the device and `out` is returned."""
+        the device and `out` is returned.  Segments of any length are searched inside the one call: short ones a lane each,
+        those beyond variant batch_lane_max (32 KiB) window by window across the whole device (profile.n_active_chunks of
+        them; profile.routed counts the ones that fell to single find calls instead -- patterns of more than 1 025 bytes,
+        variant batch_long = 0)."""
         ref = _HayRef(haystack)
         keep_off, optr, n = self._batch_offsets(ref, offsets)
         stream = _device_call_stream(ref, None)

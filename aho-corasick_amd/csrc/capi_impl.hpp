@@ -19,6 +19,7 @@
 #include "capi_internal.hpp"
 #include "device/batch_find.hpp"
 #include "device/batch_iter.hpp"
+#include "device/batch_long.hpp"
 #include "device/cnfa_walk.hpp"
 #include "device/cnfa_tri.hpp"
 #include "device/cnfa_tri_step.hpp"
@@ -115,6 +116,7 @@ struct Scratch {
     uint32_t lw_gen = 0;                           // ... generation of the overflow word (a new value per call; the word is zeroed when made)
     DevBuf hist, hcounts;                          // pattern counts (capi_count.cpp): visits[match states] + the total word; device copy of host-resident counts
     DevBuf boff, bout, blongs, bctl;               // batched find (capi_batch.cpp): device copies of host offsets / records, the list of long segments, the control words
+    DevBuf blkey, bwpre;                           // ... its long segments on the device (batch_long.hip): a key per entry of that list, the prefix of their window counts
     uint64_t* bpin = nullptr;                      // ... and the page-locked landing zone of the control words and the head of that list
     DevBuf probe;                                  // prefix-filter probe: 8 counters + the decision word at byte 64 (zeroed once)
     bool probe_ready = false;

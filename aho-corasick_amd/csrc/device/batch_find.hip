@@ -49,7 +49,10 @@ __global__ __launch_bounds__(256) void k_batch_classify(BatchArgs a) {
             atomicMin(&a.ctl[0], static_cast<unsigned long long>(s));
         } else if (e - b > a.lane_max) {
             const unsigned long long i = atomicAdd(&a.ctl[1], 1ull);
-            if (i < a.longs_cap) a.longs[i] = BatchLong{s, b, e};
+            if (i < a.longs_cap) {
+                a.longs[i] = BatchLong{s, b, e};
+                if (a.lkey) a.lkey[i] = ~0ull;   // (batch_long.hip: no occurrence seen)
+            }
         }
     }
 }
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(kBfBlock) void k_batch_find(S st, BatchArgs a) {
         if (e > a.hay_len) e = a.hay_len;
         if (e < b) e = b;
         const uint64_t vb = b + a.mis, ve = e + a.mis;   // virtual: v % 16 == 0 <=> a 16-byte aligned address
-        bool done = !valid || e - b > a.lane_max;        // (a long segment: listed by the classify kernel, served by the host)
+        bool done = !valid || e - b > a.lane_max;        // (a long segment: listed by the classify kernel, served by batch_long.hip or the host)
         bool found = false;
         uint32_t m_pid = ACGPU_NO_MATCH;
         uint64_t m_start = 0, m_end = 0;

@@ -25,6 +25,7 @@ struct BatchArgs {
     unsigned long long* ctl;   // [kBatchCtlWords]
     BatchLong* longs;          // [longs_cap]
     uint64_t longs_cap;
+    unsigned long long* lkey;  // [longs_cap] or nullptr: a key per entry of that list, set to UINT64_MAX with the entry (batch_long.hpp)
     uint32_t lane_max;
     int32_t anchored, earliest;   // (earliest: already true for a Standard automaton)
 #ifdef ACGPU_GUARD

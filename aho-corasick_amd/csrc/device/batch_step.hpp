@@ -28,6 +28,37 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     return v;
 }
 
+// The two places where a lane of try_find's loop (dev_try_find_fwd, kernels.hip; src/automaton.rs:1285-1420) looks at more
+// than the next state, as k_batch_find has them in its tile walk -- for the other walks of a segment (the resolve of
+// batch_long.hip).  k_batch_find itself keeps the text in place: called from here, the same statements inline to another
+// register allocation (56 / 56 / 53 VGPR instead of 58 / 59 / 53), and that kernel's measured code is not to change for a
+// helper's sake.  Positions are virtual; vb is the segment's begin (what an anchored match must start at).  Both return true
+// when the lane is finished (a match under earliest semantics).
+//
+// before the first byte: a match at the start state (an empty pattern)
+template <class S>
+__device__ __forceinline__ bool lane_begin(const S& st, bool earliest, uint64_t at, uint32_t sid, bool& found, uint32_t& m_pid,
+                                           uint64_t& m_start, uint64_t& m_end) {
+    if (!st.is_match(sid)) return false;
+    uint32_t pid, plen;
+    st.first(sid, pid, plen);
+    m_pid = pid; m_end = at; m_start = at - plen;
+    found = true;
+    return earliest;
+}
+// behind a byte that led to the match state `sid`; me: the position behind that byte
+template <class S>
+__device__ __forceinline__ bool lane_match(const S& st, bool anchored, bool earliest, uint64_t vb, uint64_t me, uint32_t sid,
+                                           bool& found, uint32_t& m_pid, uint64_t& m_start, uint64_t& m_end) {
+    uint32_t pid, plen;
+    st.first(sid, pid, plen);
+    const uint64_t ms = me - plen;
+    if (anchored && ms > vb) return false;
+    m_pid = pid; m_start = ms; m_end = me;
+    found = true;
+    return earliest;
+}
+
 template <class E>
 struct GlobalStep {
     E eng;

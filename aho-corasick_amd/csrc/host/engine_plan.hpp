@@ -85,6 +85,40 @@ inline BatchForm plan_batch(const BatchFacts& f) {
     return f.has_dfa ? BatchForm::DfaWalk : BatchForm::CnfaWalk;
 }
 
+// Who serves the segments of a batched find that are longer than a lane walks (capi_batch.cpp / device/batch_long.hip;
+// DESIGN.md 3.2d "Long segments").  The device form needs one position p* per segment from which the lane loop on the
+// automaton's own tables reports the segment's answer within max_pattern_len bytes: the segment's begin for an anchored
+// search or a set with an empty pattern (Resolve), else a minimum over the occurrences of the Standard automaton of the same
+// patterns, taken by a scout kernel that streams windows of the segment through the walk's LDS tile (ScoutResolve).  A
+// window and its warm-up of max_pattern_len - 1 bytes share that tile: patterns whose warm-up would take more than
+// kBatchLongWarmMax of it, and patterns longer than a lane walks, keep the single-span calls (HostCalls).
+constexpr uint32_t kBatchLongWarmMax = kBatchTile / 8;
+struct BatchLongFacts {
+    bool anchored = false;            // acgpu_input.anchored
+    bool standard = true;             // the automaton's match kind is Standard
+    bool has_twin = false;            // ... or it has a Standard twin of the same patterns (acgpu_automaton::occ)
+    bool occ_anchored_only = false;   // start kind of the automaton the scout would walk (the twin, else the automaton itself)
+    bool split = false;               // the automaton or its twin is a split set (searched through its parts)
+    size_t n_patterns = 0, min_pattern_len = 0, max_pattern_len = 0;
+    uint32_t lane_max = kBatchLaneMaxDefault;
+    bool batch_long = true;           // variant `batch_long`
+};
+enum class BatchLongForm : uint32_t { HostCalls = 0, Resolve = 1, ScoutResolve = 2 };
+inline BatchLongForm plan_batch_long(const BatchLongFacts& f) {
+    if (!f.batch_long || f.split || f.max_pattern_len > f.lane_max) return BatchLongForm::HostCalls;
+    if (f.anchored || (f.n_patterns > 0 && f.min_pattern_len == 0)) return BatchLongForm::Resolve;
+    if (f.n_patterns == 0 || (!f.standard && !f.has_twin) || f.occ_anchored_only) return BatchLongForm::HostCalls;
+    if (f.max_pattern_len - 1 > kBatchLongWarmMax) return BatchLongForm::HostCalls;
+    return BatchLongForm::ScoutResolve;
+}
+// bytes of a long segment whose match ENDS one wavefront of the scout owns per tile: the tile less the 16-byte aligned hull
+// of the warm-up, a multiple of 64 so that every lane owns a whole number of bytes (>= 64 under kBatchLongWarmMax)
+inline uint32_t batch_long_window(size_t max_pattern_len) {
+    const uint32_t hull = (uint32_t(max_pattern_len) - 1 + 15 + 15) & ~15u;
+    return (kBatchTile - hull) & ~63u;
+}
+static_assert(((kBatchTile - ((kBatchLongWarmMax + 30) & ~15u)) & ~63u) >= 64 * 64, "a lane owns at least 64 bytes");
+
 // Which stepper the batched iterator walks with (acgpu_find_iter_batch, capi_batch_iter.cpp / device/batch_iter.hip): plan_batch's
 // answer, except that its fill pass keeps kBatchIterStage records per wavefront in LDS beside the tiles (a task's records
 // are put together there and stored as one piece), so the rows form is chosen only when the image fits what that leaves of

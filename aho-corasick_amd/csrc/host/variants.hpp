@@ -39,8 +39,9 @@ struct Variants {
     int32_t stream_split = 0;       // 1: feed large chunks as two halves
     // batched find (capi_batch.cpp, device/batch_find.hip)
     int32_t batch_rows = 1;         // 0: never walk the LDS image of the DFA (the global steppers on a small automaton)
-    int32_t batch_lane_max = 0;     // longest segment a lane walks, bytes (0: 32 KiB); longer ones are served by acgpu_find
+    int32_t batch_lane_max = 0;     // longest segment a lane walks, bytes (0: 32 KiB); longer ones are served by batch_long.hip or by acgpu_find
     int32_t batch_blocks = 0;       // workgroups of the walk (0: as many as the device holds)
+    int32_t batch_long = 1;         // 0: the long segments are never served on the device (batch_long.hip), always by acgpu_find
 
     // name -> field (nullptr: unknown name)
     int32_t* field(const char* name) {
@@ -49,7 +50,7 @@ struct Variants {
         ACGPU_VARIANT(pfx_tails) ACGPU_VARIANT(pfx_key8) ACGPU_VARIANT(pfx_key8_x2) ACGPU_VARIANT(pfx_short) ACGPU_VARIANT(walk_literal)
         ACGPU_VARIANT(walk_tri) ACGPU_VARIANT(tri_events) ACGPU_VARIANT(pf_classic) ACGPU_VARIANT(routing) ACGPU_VARIANT(eo_fused) ACGPU_VARIANT(start_table)
         ACGPU_VARIANT(ss_window_kib) ACGPU_VARIANT(find_iter_windows) ACGPU_VARIANT(find_iter_start_table) ACGPU_VARIANT(find_iter_disjoint) ACGPU_VARIANT(stream_split)
-        ACGPU_VARIANT(batch_rows) ACGPU_VARIANT(batch_lane_max) ACGPU_VARIANT(batch_blocks)
+        ACGPU_VARIANT(batch_rows) ACGPU_VARIANT(batch_lane_max) ACGPU_VARIANT(batch_blocks) ACGPU_VARIANT(batch_long)
 #undef ACGPU_VARIANT
         return nullptr;
     }

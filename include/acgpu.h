@@ -159,7 +159,7 @@ typedef struct acgpu_automaton acgpu_automaton;
  *   walk_literal 0|1, walk_tri 0|1, tri_events 0|1                     transition walks
  *   pf_classic 0|1, routing 0|1, eo_fused 0|1                          prefix filter result form / hand-over of abandoned scans / the order pass's histogram inside the scan
  *   start_table 0|1, ss_window_kib n, find_iter_windows 0|1, find_iter_start_table 0|1, find_iter_disjoint 0|1, stream_split 0|1   non-overlapping forms
- *   batch_rows 0|1, batch_lane_max bytes, batch_blocks n                acgpu_find_batch: never the LDS image | longest segment a lane walks (0: 32 KiB) | workgroups of the walk (0: what the device holds)
+ *   batch_rows 0|1, batch_lane_max bytes, batch_blocks n, batch_long 0|1   acgpu_find_batch: never the LDS image | longest segment a lane walks (0: 32 KiB) | workgroups of the walk (0: what the device holds) | longer segments never on the device, always by acgpu_find
  * Unknown names and automata that are already on a device: ACGPU_ERR_INVALID_ARGUMENT. */
 acgpu_status acgpu_set_variant(acgpu_automaton* aut, const char* name, int32_t value);
 
@@ -246,9 +246,12 @@ acgpu_status acgpu_count_patterns(acgpu_automaton* aut, const acgpu_input* input
  *     ACGPU_ERR_INVALID_ARGUMENT with the reason in acgpu_last_error() (`out` is then unspecified).  n_segments == 0: ACGPU_OK,
  *     the device is not touched.
  * One segment per wavefront lane walks the reference's try_find loop from the automaton's own start state;
- * segments longer than variant batch_lane_max are served by acgpu_find on their span.  Synchronous.  prof: ms_scan the walk,
- * ms_compact the classification in front of it, n_chunks the wave tasks, n_active_chunks the segments handed to acgpu_find,
- * n_matches the segments with a match, engine_used the stepper (LDS_WALK: the DFA as u16 rows in LDS). */
+ * segments longer than variant batch_lane_max are searched window by window across the device inside the same
+ * synchronisation (DESIGN.md 3.2d "Long segments") -- or, for patterns longer than 1 025 bytes or than batch_lane_max, split
+ * sets, leftmost automata without a Standard twin and variant batch_long = 0, by acgpu_find on their span afterwards.
+ * Synchronous.  prof: ms_scan the walk, ms_compact the classification in front of it, ms_fill the long segments on the
+ * device, n_chunks the wave tasks, n_active_chunks the segments longer than batch_lane_max, routed those of them handed to
+ * acgpu_find, n_matches the segments with a match, engine_used the stepper (LDS_WALK: the DFA as u16 rows in LDS). */
 #define ACGPU_NO_MATCH 0xFFFFFFFFu
 acgpu_status acgpu_find_batch(acgpu_automaton* aut, const acgpu_input* input, const uint64_t* offsets, size_t n_segments,
                               acgpu_match* out, acgpu_profile* prof);

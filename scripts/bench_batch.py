@@ -3,7 +3,11 @@
   lines-6words   the lines of the prose corpus as segments x a 6-word set (LDS rows)
   lines-dict     the same segments x the reference's words-5000 dictionary (global stepper)
   fixed128       128-byte segments of the Appendix-C text x the headline set, variant batch_rows = 0 and automatic
-  one-percent    128-byte segments, every 100th one longer than batch_lane_max (served by acgpu_find)
+  one-percent    128-byte segments, every 100th one longer than batch_lane_max: on the device (device/batch_long.hip), and
+                 with variant batch_long = 0 by one acgpu_find call each
+  all-long       the same text cut into 40 KiB segments, both forms
+  one-huge       1, 8 and 64 MiB of the same text as ONE segment, both forms, beside a plain find call on the span;
+                 one-huge-no-match: the same with a one-word set that the text does not hold
   loop           the yardstick: one find call per segment over the first 4 096 lines, against one find_batch call
   chunked-walk   ms_scan of the rows form against k_lw_count (the chunked LDS walk) over the same bytes
 Per row: GB/s of packed bytes and segments/s of the whole call (host clock, median of alternating rounds after a warm-up),
@@ -25,6 +29,7 @@ args = ap.parse_args()
 N = args.mib << 20
 WORDS6 = [b"Sherlock", b"Holmes", b"Watson", b"London", b"which", b"the "]
 prof = _lib.CProfile()
+SPREAD = {}
 
 
 def build(pats, kind=None, engine="auto", **variants):
@@ -50,6 +55,7 @@ def alternate(fns, steps):
     for _ in range(steps):
         for k, f in fns.items():
             ms[k].append(f())
+    SPREAD.update({k: (min(v), max(v)) for k, v in ms.items()})   # the run-to-run spread of the rounds
     return {k: float(np.median(v)) for k, v in ms.items()}
 
 
@@ -67,7 +73,7 @@ def row(name, auts, buf, off, **extra):
     def call(label, a):
         def f():
             ms = wall(lambda: a.find_batch(buf, off, out=out, profile=prof))
-            scan[label] = (float(prof.ms_scan), int(prof.engine_used), int(prof.n_active_chunks))
+            scan[label] = (float(prof.ms_scan), int(prof.engine_used), int(prof.n_active_chunks), float(prof.ms_fill), int(prof.routed))
             return ms
         return f
     ms = alternate({label: call(label, a) for label, a in auts.items()}, args.steps)
@@ -75,7 +81,8 @@ def row(name, auts, buf, off, **extra):
     for label in auts:
         print(json.dumps({"row": name, "form": label, "segments": n, "bytes": nbytes, "matching_segments": hits,
                           "call_ms": round(ms[label], 4), "ms_scan": round(scan[label][0], 4), "stepper": scan[label][1],
-                          "long_segments": scan[label][2], "GBps": round(nbytes / ms[label] / 1e6, 2),
+                          "long_segments": scan[label][2], "ms_long": round(scan[label][3], 4), "host_find_calls": scan[label][4],
+                          "spread_ms": [round(x, 4) for x in SPREAD[label]], "GBps": round(nbytes / ms[label] / 1e6, 2),
                           "Msegments_per_s": round(n / ms[label] / 1e3, 2), **extra}), flush=True)
     return ms
 
@@ -98,7 +105,22 @@ lens = np.full(N // 128, 128, dtype=np.int64)
 lens[::100] = 40 << 10
 mixed = np.concatenate([[0], np.cumsum(lens)])
 mixed = torch.from_numpy(mixed[mixed <= N]).cuda()
-row("one-percent", {"auto": build(headline, ac.AhoCorasickKind.DFA)}, synth, mixed)
+dev_long, host_long = build(headline, ac.AhoCorasickKind.DFA), build(headline, ac.AhoCorasickKind.DFA, batch_long=0)
+row("one-percent", {"device": dev_long, "host_calls": host_long}, synth, mixed)
+row("all-long", {"device": dev_long, "host_calls": host_long}, synth, torch.arange(0, N + 1, 40 << 10, dtype=torch.int64, device="cuda"))
+# (a ceiling on the device path could only hand a huge segment to the host_calls form, so that is what it has to beat;
+#  match-poor text: a set of one word the text does not hold, so every window is walked)
+absent = b"\x00zq\x00absent\x00"
+assert absent not in bytes(synth.cpu().numpy())
+for name, pats in (("one-huge", headline), ("one-huge-no-match", [absent])):
+    dev_h, host_h = (dev_long, host_long) if pats is headline else (build(pats, ac.AhoCorasickKind.DFA), build(pats, ac.AhoCorasickKind.DFA, batch_long=0))
+    for size in sorted({min(N, m << 20) for m in (1, 8, 64)}):
+        huge = torch.tensor([0, size], dtype=torch.int64, device="cuda")
+        ms = row(name, {"device": dev_h, "host_calls": host_h}, synth[:size], huge)
+        find_ms = alternate({"find": lambda: wall(lambda: dev_h.find(ac.Input(synth).range(0, size)))}, args.steps)
+        print(json.dumps({"row": name, "form": "single find call", "bytes": size, "call_ms": round(find_ms["find"], 4),
+                          "spread_ms": [round(x, 4) for x in SPREAD["find"]], "device_over_find": round(ms["device"] / find_ms["find"], 2),
+                          "device_over_host_calls": round(ms["device"] / ms["host_calls"], 2)}), flush=True)
 
 # ---- the yardstick: a loop of find calls over 4 096 segments (what a caller had before) against one batch call
 k = 4096
