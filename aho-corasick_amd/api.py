@@ -720,7 +720,9 @@ class AhoCorasick:
         (as find_batch takes them) return (records: MATCH_DTYPE array, rec_off: uint64 array of len(offsets)).  With out= a
         CUDA uint8 tensor and rec_offsets= a CUDA int64 tensor of len(offsets) elements, a CUDA haystack with CUDA offsets is
         searched zero-copy on torch's current stream and both results stay on the device: returns (n_records, ok), ok =
-        False when `out` holds fewer than n_records records (nothing usable was written to it)."""
+        False when `out` holds fewer than n_records records (nothing usable was written to it).  Segments longer than variant
+        batch_lane_max (32 KiB) are searched window by window on the device with overlapping=True; otherwise, and for split
+        sets, patterns beyond 1 025 bytes and variant batch_long = 0, by one single-span call each (profile.routed counts them)."""
         ref = _HayRef(haystack)
         keep_off, optr, n = self._batch_offsets(ref, offsets)
         on_dev = out is not None or rec_offsets is not None

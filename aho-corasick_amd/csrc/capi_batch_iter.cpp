@@ -1,9 +1,12 @@
 // C ABI of libacgpu.so, batched iterator (acgpu_find_iter_batch): every match of every segment of a packed haystack, CSR
 // output, one call for millions of short texts.  control words + classify (device/batch_find.hip) -> count
 // (device/batch_iter.hip) -> scan (launch_scan) -> SYNCHRONISATION 1: the offsets' error flag, the total, the list of the
-// segments too long for a lane -> capacity check -> fill -> result copies -> SYNCHRONISATION 2.  The long segments (rare) are
-// served between the two by acgpu_find_iter / acgpu_find_overlapping on their span: their counts are patched on the device,
-// the scan runs again, and their records are put at rec_off[seg] behind the fill.  See capi_batch.cpp.
+// segments too long for a lane -> capacity check -> fill -> result copies -> SYNCHRONISATION 2.  The long segments of an
+// overlapping call are served on the device where plan_batch_iter_long says so (device/batch_iter_long.hip): window-count scan,
+// count and prefix in front of the scan -- which then covers short and long segments alike --, their fill behind the fill;
+// two synchronisations however many there are.  Otherwise they are served between the two by acgpu_find_iter /
+// acgpu_find_overlapping on their span: their counts are patched on the device, the scan runs again, and their records are
+// put at rec_off[seg] behind the fill.  See capi_batch.cpp.
 #include "capi_impl.hpp"
 
 using namespace acgpu;
@@ -59,9 +62,16 @@ extern "C" acgpu_status acgpu_find_iter_batch(acgpu_automaton* aut, const acgpu_
     acgpu_automaton* twin = nullptr;   // (not used: every stepper walks the automaton's own tables)
     acgpu_status st = overlapping ? check_overlapping(aut, &whole, &twin) : check_nonoverlapping(aut, &whole);
     if (st) return st;
-    if (!in->haystack_on_device)   // host offsets: refused here; device offsets: by the classify kernel, same message
-        for (size_t s = 0; s < n; s++)
+    const uint32_t lane_max = aut->var.batch_lane_max > 0 ? uint32_t(aut->var.batch_lane_max) : kBatchLaneMaxDefault;
+    // an upper bound of the long segments: counted where the offsets are the host's, else what the haystack has room for
+    uint64_t max_long = std::min<uint64_t>(n, in->haystack_len / (uint64_t(lane_max) + 1));
+    if (!in->haystack_on_device) {   // host offsets: refused here; device offsets: by the classify kernel, same message
+        max_long = 0;
+        for (size_t s = 0; s < n; s++) {
             if (offsets[s + 1] < offsets[s] || offsets[s + 1] > in->haystack_len) return bad_argument(batch_bad_offsets_text(s));
+            max_long += offsets[s + 1] - offsets[s] > lane_max;
+        }
+    }
 
     // ---- device inputs
     DeviceState* ds = nullptr;
@@ -100,7 +110,7 @@ extern "C" acgpu_status acgpu_find_iter_batch(acgpu_automaton* aut, const acgpu_
     a.off = doff; a.n_seg = n; a.out = nullptr;
     a.ctl = sc->bctl.as<unsigned long long>();
     a.longs = sc->blongs.as<BatchLong>(); a.longs_cap = n;
-    a.lane_max = ds->var.batch_lane_max > 0 ? uint32_t(ds->var.batch_lane_max) : kBatchLaneMaxDefault;
+    a.lane_max = lane_max;
     a.anchored = in->anchored != 0;
     a.earliest = in->earliest != 0 || aut->cfg.match_kind == ACGPU_MATCH_STANDARD;   // FindIter keeps the caller's flag (automaton.rs:864-883)
 #ifdef ACGPU_GUARD
@@ -121,24 +131,52 @@ extern "C" acgpu_status acgpu_find_iter_batch(acgpu_automaton* aut, const acgpu_
     }
     const uint32_t blocks = uint32_t(std::max(ds->var.batch_blocks, 0));
 
-    // ---- classify -> count -> scan -> the control words, the total and the head of the long list: synchronisation 1
+    // ---- the long segments: on the device, or by the host after synchronisation 1; a call that cannot have any queues
+    // nothing for them.  Scratch is sized by what the host knows now: a segment of k bytes has ceil(k / window) windows
+    const bool on_device = plan_batch_iter_long(batch_long_facts(aut, in, lane_max), overlapping != 0) == BatchIterLongForm::WindowWalk;
+    const bool dev_long = on_device && max_long > 0;
+    BatchLongArgs la{};
+    BatchIterLongArgs ila{};
+    if (dev_long) {
+        la.max_len = uint32_t(aut->nnfa.max_pattern_len);
+        la.window = batch_long_window(aut->nnfa.max_pattern_len);
+        ila.cap_windows = (hi - lo) / la.window + max_long;
+        HIP_TRY(sc->bwpre.ensure((n + 1) * sizeof(uint64_t)));
+        HIP_TRY(sc->bilane.ensure(ila.cap_windows * 64 * sizeof(uint32_t)));
+        HIP_TRY(sc->biwsum.ensure(ila.cap_windows * sizeof(uint64_t)));
+        la.wpre = sc->bwpre.as<uint64_t>();
+        ila.lane_cnt = sc->bilane.as<uint32_t>();
+        ila.wsum = sc->biwsum.as<uint64_t>();
+    }
+
+    // ---- classify -> count -> (window-count scan -> count -> prefix of the long segments) -> scan -> the control words, the
+    // total and, where the host serves them, the head of the long list: synchronisation 1
     if (prof) HIP_TRY(hipEventRecord(sc->ev[0], stream));
     HIP_TRY(launch_batch_classify(a, stream));
     HIP_TRY(launch_batch_iter_count(uint32_t(form), ds->da, rows, ia, blocks, stream));
+    if (dev_long) {
+        if (prof) HIP_TRY(hipEventRecord(sc->ev[4], stream));
+        HIP_TRY(launch_batch_long_scan(a, la, stream));
+        HIP_TRY(launch_batch_iter_long_count(uint32_t(form), ds->da, rows, ia, la, ila, blocks, stream));
+        HIP_TRY(launch_batch_iter_long_prefix(ia, la, ila, max_long, stream));
+        if (prof) HIP_TRY(hipEventRecord(sc->ev[5], stream));
+    }
     HIP_TRY(launch_scan(ss, n, stream));
     HIP_TRY(launch_batch_iter_seal(ss.totals, drec + n, stream));
     if (prof) HIP_TRY(hipEventRecord(sc->ev[1], stream));
-    const size_t head = std::min<size_t>(n, kBatchListHead);
+    const size_t head = on_device ? 0 : std::min<size_t>(n, kBatchListHead);
     HIP_TRY(hipMemcpyAsync(sc->bpin, a.ctl, kBatchCtlWords * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(sc->bpin + kBatchCtlWords, a.longs, head * sizeof(BatchLong), hipMemcpyDeviceToHost, stream));
+    if (head) HIP_TRY(hipMemcpyAsync(sc->bpin + kBatchCtlWords, a.longs, head * sizeof(BatchLong), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    const uint64_t bad = sc->bpin[0], n_long = sc->bpin[1];
+    const uint64_t bad = sc->bpin[0], n_all_long = sc->bpin[1];
     if (bad != ~uint64_t(0)) return bad_argument(batch_bad_offsets_text(bad));
-    if (n_long > n) return ACGPU_ERR_HIP;
+    if (n_all_long > n || (on_device && n_all_long > max_long)) return ACGPU_ERR_HIP;
+    if (dev_long && sc->bpin[2]) return bad_argument("a segment has 2^32 records or more");   // (control word [2]: the prefix kernel's)
     uint64_t total = sc->pinned[0];
 
-    // ---- the long segments: the single-span call on each (the haystack is on the device by now), their counts patched on
-    // the device, the scan again
+    // ---- the long segments the device did not serve: the single-span call on each (the haystack is on the device by now),
+    // their counts patched on the device, the scan again
+    const uint64_t n_long = on_device ? 0 : n_all_long;
     std::vector<BatchLong> longs(n_long);
     std::vector<std::vector<acgpu_match>> long_recs(n_long);
     std::vector<uint32_t> long_counts(n_long);
@@ -166,7 +204,8 @@ extern "C" acgpu_status acgpu_find_iter_batch(acgpu_automaton* aut, const acgpu_
     if (prof) {
         prof->bytes_scanned = hi - lo;
         prof->n_chunks = (n + 63) / 64;       // wave tasks
-        prof->n_active_chunks = n_long;       // segments served by the single-span calls
+        prof->n_active_chunks = n_all_long;   // segments longer than a lane walks ...
+        prof->routed = uint32_t(std::min<uint64_t>(n_long, UINT32_MAX));   // ... and those of them that the single-span calls served
         prof->n_matches = total;
         prof->engine_used = uint32_t(form);   // (BatchForm is numbered as acgpu_engine)
     }
@@ -175,6 +214,7 @@ extern "C" acgpu_status acgpu_find_iter_batch(acgpu_automaton* aut, const acgpu_
         if (prof) {
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, sc->ev[0], sc->ev[1])); prof->ms_compact = ms; prof->ms_total = ms;
+            if (dev_long) { HIP_TRY(hipEventElapsedTime(&ms, sc->ev[4], sc->ev[5])); prof->ms_fill = ms; }
         }
         return ACGPU_ERR_BUFFER_TOO_SMALL;
     }
@@ -186,6 +226,10 @@ extern "C" acgpu_status acgpu_find_iter_batch(acgpu_automaton* aut, const acgpu_
     if (prof) HIP_TRY(hipEventRecord(sc->ev[2], stream));
     if (total) HIP_TRY(launch_batch_iter_fill(uint32_t(form), ds->da, rows, ia, blocks, stream));
     if (prof) HIP_TRY(hipEventRecord(sc->ev[3], stream));
+    if (dev_long) {   // (behind the fill: a staged task of k_batch_iter stores its whole range, a long segment's part included)
+        if (total) HIP_TRY(launch_batch_iter_long_fill(uint32_t(form), ds->da, rows, ia, la, ila, blocks, stream));
+        if (prof) HIP_TRY(hipEventRecord(sc->ev[6], stream));
+    }
     for (size_t i = 0; i < n_long; i++)
         if (long_counts[i])
             HIP_TRY(hipMemcpyAsync(dout + long_at[i], long_recs[i].data(), long_counts[i] * sizeof(acgpu_match), hipMemcpyHostToDevice, stream));
@@ -199,7 +243,13 @@ extern "C" acgpu_status acgpu_find_iter_batch(acgpu_automaton* aut, const acgpu_
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, sc->ev[0], sc->ev[1])); prof->ms_compact = ms;   // classification + count + scan
         HIP_TRY(hipEventElapsedTime(&ms, sc->ev[2], sc->ev[3])); prof->ms_scan = ms;      // fill
-        HIP_TRY(hipEventElapsedTime(&ms, sc->ev[0], sc->ev[3])); prof->ms_total = ms;
+        HIP_TRY(hipEventElapsedTime(&ms, sc->ev[0], sc->ev[dev_long ? 6 : 3])); prof->ms_total = ms;
+        if (dev_long) {   // the long segments on the device: window-count scan + count + prefix (inside ms_compact), and their fill
+            float ms_fill = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, sc->ev[4], sc->ev[5]));
+            HIP_TRY(hipEventElapsedTime(&ms_fill, sc->ev[3], sc->ev[6]));
+            prof->ms_fill = ms + ms_fill;
+        }
     }
     return ACGPU_OK;
 }

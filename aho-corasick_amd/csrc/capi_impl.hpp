@@ -19,6 +19,7 @@
 #include "capi_internal.hpp"
 #include "device/batch_find.hpp"
 #include "device/batch_iter.hpp"
+#include "device/batch_iter_long.hpp"
 #include "device/batch_long.hpp"
 #include "device/cnfa_walk.hpp"
 #include "device/cnfa_tri.hpp"
@@ -117,6 +118,7 @@ struct Scratch {
     DevBuf hist, hcounts;                          // pattern counts (capi_count.cpp): visits[match states] + the total word; device copy of host-resident counts
     DevBuf boff, bout, blongs, bctl;               // batched find (capi_batch.cpp): device copies of host offsets / records, the list of long segments, the control words
     DevBuf blkey, bwpre;                           // ... its long segments on the device (batch_long.hip): a key per entry of that list, the prefix of their window counts
+    DevBuf bilane, biwsum;                         // batched iterator, long segments on the device (batch_iter_long.hip): records per lane and per window
     uint64_t* bpin = nullptr;                      // ... and the page-locked landing zone of the control words and the head of that list
     DevBuf probe;                                  // prefix-filter probe: 8 counters + the decision word at byte 64 (zeroed once)
     bool probe_ready = false;
@@ -384,6 +386,7 @@ acgpu_status enqueue_impl(acgpu_automaton* aut, const acgpu_input* in, size_t sh
                           EnqueueSync* sync = nullptr);
 // ---- capi_batch.cpp (shared with the batched iterator, capi_batch_iter.cpp)
 BatchFacts batch_facts(const DeviceState* ds);
+BatchLongFacts batch_long_facts(const acgpu_automaton* aut, const acgpu_input* in, uint32_t lane_max);   // the inputs of plan_batch_long / plan_batch_iter_long
 constexpr size_t kBatchListHead = 1024;   // entries of the long-segment list that arrive with the control words (Scratch::bpin)
 std::string batch_bad_offsets_text(uint64_t seg);   // offsets[seg + 1] decreases or passes the haystack
 // ---- capi_find.cpp

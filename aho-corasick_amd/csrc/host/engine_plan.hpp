@@ -119,6 +119,19 @@ inline uint32_t batch_long_window(size_t max_pattern_len) {
 }
 static_assert(((kBatchTile - ((kBatchLongWarmMax + 30) & ~15u)) & ~63u) >= 64 * 64, "a lane owns at least 64 bytes");
 
+// Who serves the long segments of a batched iterator (capi_batch_iter.cpp / device/batch_iter_long.hip; DESIGN.md 3.2e "Long
+// segments").  The OVERLAPPING iteration has a device form: its records depend on the end position and the state there
+// alone, and the state is known max_pattern_len - 1 bytes into a walk from the start state, so the windows of the scout
+// above each emit their own records (WindowWalk) -- under the scout's limits on the warm-up.  The non-overlapping iteration
+// of every match kind restarts where the last match ended, a chain across windows: it keeps the single-span calls, as do
+// split sets, sets without a pattern and variant batch_long = 0.
+enum class BatchIterLongForm : uint32_t { HostCalls = 0, WindowWalk = 1 };
+inline BatchIterLongForm plan_batch_iter_long(const BatchLongFacts& f, bool overlapping) {
+    if (!overlapping || !f.batch_long || f.split || f.n_patterns == 0) return BatchIterLongForm::HostCalls;
+    if (f.max_pattern_len > f.lane_max || f.max_pattern_len > kBatchLongWarmMax + 1) return BatchIterLongForm::HostCalls;
+    return BatchIterLongForm::WindowWalk;
+}
+
 // Which stepper the batched iterator walks with (acgpu_find_iter_batch, capi_batch_iter.cpp / device/batch_iter.hip): plan_batch's
 // answer, except that its fill pass keeps kBatchIterStage records per wavefront in LDS beside the tiles (a task's records
 // are put together there and stored as one piece), so the rows form is chosen only when the image fits what that leaves of

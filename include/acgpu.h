@@ -159,7 +159,7 @@ typedef struct acgpu_automaton acgpu_automaton;
  *   walk_literal 0|1, walk_tri 0|1, tri_events 0|1                     transition walks
  *   pf_classic 0|1, routing 0|1, eo_fused 0|1                          prefix filter result form / hand-over of abandoned scans / the order pass's histogram inside the scan
  *   start_table 0|1, ss_window_kib n, find_iter_windows 0|1, find_iter_start_table 0|1, find_iter_disjoint 0|1, stream_split 0|1   non-overlapping forms
- *   batch_rows 0|1, batch_lane_max bytes, batch_blocks n, batch_long 0|1   acgpu_find_batch: never the LDS image | longest segment a lane walks (0: 32 KiB) | workgroups of the walk (0: what the device holds) | longer segments never on the device, always by acgpu_find
+ *   batch_rows 0|1, batch_lane_max bytes, batch_blocks n, batch_long 0|1   acgpu_find_batch: never the LDS image | longest segment a lane walks (0: 32 KiB) | workgroups of the walk (0: what the device holds) | longer segments never on the device, always by acgpu_find (acgpu_find_iter_batch: by the single-span iterator calls)
  * Unknown names and automata that are already on a device: ACGPU_ERR_INVALID_ARGUMENT. */
 acgpu_status acgpu_set_variant(acgpu_automaton* aut, const char* name, int32_t value);
 
@@ -272,10 +272,15 @@ acgpu_status acgpu_find_batch(acgpu_automaton* aut, const acgpu_input* input, co
  *     acgpu_last_error()).  n_segments == 0: ACGPU_OK, *n_out = 0, the device is not touched: host rec_offsets[0] = 0 is
  *     stored, device rec_offsets are left as they are.
  * Two passes of one segment per wavefront lane -- count, prefix sum, fill; only segments with matches are walked twice --
- * and two synchronisations; segments longer than variant batch_lane_max are served by acgpu_find_iter /
- * acgpu_find_overlapping on their span.  The variants of acgpu_find_batch apply.  prof: ms_compact classification + count +
- * prefix sum, ms_scan the fill, n_chunks the wave tasks, n_active_chunks the segments handed to the single-span calls,
- * n_matches the total, engine_used the stepper; with ACGPU_ERR_BUFFER_TOO_SMALL the counts and ms_compact = ms_total. */
+ * and two synchronisations.  Segments longer than variant batch_lane_max: with overlapping != 0 they are
+ * counted and filled window by window across the device inside the same two synchronisations (DESIGN.md 3.2e "Long
+ * segments"); a non-overlapping call, a split set, a set without patterns, patterns longer than 1 025 bytes or than
+ * batch_lane_max and variant batch_long = 0 hand them to acgpu_find_iter / acgpu_find_overlapping on their span.  The variants
+ * of acgpu_find_batch apply.  prof: ms_compact classification + count + prefix sum (the count of long segments on the device
+ * included), ms_scan the fill, ms_fill the launches for long segments on the device (their count and their fill), ms_total up
+ * to the last fill, n_chunks the wave tasks, n_active_chunks the segments longer than batch_lane_max, routed those of them
+ * handed to the single-span calls, n_matches the total, engine_used the stepper; with ACGPU_ERR_BUFFER_TOO_SMALL the counts
+ * and ms_compact = ms_total. */
 acgpu_status acgpu_find_iter_batch(acgpu_automaton* aut, const acgpu_input* input, const uint64_t* offsets, size_t n_segments,
                                    int overlapping, uint64_t* rec_offsets, acgpu_match* out, size_t cap, size_t* n_out,
                                    acgpu_profile* prof);
